@@ -9,14 +9,25 @@ synthetic LJSpeech-shaped batch per GPU (config 2 of BASELINE.json: 4+4 FFT laye
 batch 48 per GPU, ~128 phonemes -> ~900 frames, bf16 compute with fp32 master weights), inputs resident in HBM.
 value = sum of valid mel frames over all ranks and K steps / max-over-ranks wall time.
 
-The same JSON line carries
+A plain run sets up, warms up, times exactly K steps, and prints the line: metric, value, unit, higher_is_better, dtype,
+ms_per_step (one timed step) and a config object; roofline and cpu_baseline are null.
+    --dump-outputs DIR   after the timed steps, write what the last timed step computed (losses, the forward outputs, a fixed
+                         sample of the updated parameters; in --mode synth the last batch's PCM and mel) as DIR/<name>.npy.
+                         Inputs and weights are seeded, and the last timed step starts from the seeded initial training
+                         state (put back outside the timing, TrainState), so two runs dump the same step to rounding
+    --full               everything below as well, and the timed region repeated --windows (default 5) times with the
+                         median window reported
+
+With --full the same JSON line carries
   roofline     — the dominant kernel (conv_gemm MFMA contraction): algorithmic FLOPs of its launches / their HIP-event
                  durations, measured in an instrumented replay of the same step right after the timed region; plus
                  `wgrad_family`: the weight-gradient kernels of the same replay (the largest block of device time);
   cpu_baseline — the CPU oracle (a port of the reference algorithm, oracle/fs2_oracle.py; the reference tree itself is not
                  on the GPU box) timed on this host's cores on a bounded sample of the same workload: B=4, BASELINE.md §2's
                  10 steps with 2 discarded, at the best of a torch-thread sweep.  Reported, not a target;
-  config.synth — the second half of BASELINE's metric, batch-synthesis RTF on a val.txt-shaped workload (N = 1 only).
+  config.synth — the second half of BASELINE's metric, batch-synthesis RTF on a val.txt-shaped workload (N = 1 only);
+  config.fp32_* — the same step in fp32 compute; config.hip_graph_* — the step replayed from a captured hipGraph;
+  N > 1: per-rank local step times and whether the replicas' parameters are bit-identical after the timed steps.
 """
 import argparse
 import json
@@ -70,8 +81,14 @@ def parse(argv=None):
     ap.add_argument("--frame-level", action="store_true", help="frame-level pitch/energy (the paper's configuration) instead of phoneme-level")
     ap.add_argument("--side-stream", type=int, default=1, help="1: weight gradients on a side HIP stream (default, what train.py does); "
                                                                 "0: single stream (for per-kernel profiling)")
-    ap.add_argument("--windows", type=int, default=5, help="the timed region is repeated this many times (each = --steps steps, "
-                                                          "barrier + sync on both sides); the MEDIAN window is reported")
+    ap.add_argument("--windows", type=int, default=None, help="the timed region is repeated this many times (each = --steps steps, "
+                                                             "barrier + sync on both sides); the MEDIAN window is reported "
+                                                             "(default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements (roofline, cpu_baseline, fp32, synth, hipGraph "
+                                                        "line, per-rank local steps) and the repeated timed window; a plain run only "
+                                                        "times the --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     ap.add_argument("--no-fp32", action="store_true", help="skip the secondary fp32 (the reference's own arithmetic) step time")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -87,6 +104,10 @@ def parse(argv=None):
                          "line is the configuration the one-rank line was measured on; an exported value wins; 0 = runtime default)")
     ap.add_argument("--cpu-threads", default="8,16,32,64", help="torch thread counts the CPU baseline sweeps (those <= cpu_count)")
     a = ap.parse_args(argv)
+    if a.windows is None:
+        a.windows = 5 if a.full else 1
+    if not a.full:                               # a plain run measures its headline figure and nothing else
+        a.no_fp32 = a.no_cpu_baseline = a.no_roofline = a.no_graph_line = a.no_synth = True
     argv = sys.argv if argv is None else argv
     if a.mode == "synth":                        # one pass over the val.txt-shaped batches by default (64 batches of 8)
         if "--steps" not in argv:
@@ -162,7 +183,8 @@ def build(args, device, rank, world, dtype=None):
     return model, loss_fn, opt, b, pcfg, mcfg
 
 
-def make_step(model, loss_fn, opt, b, exchange):
+def make_step(model, loss_fn, opt, b, exchange, last=None):
+    """-> (step, fwd_bwd).  `last`: a dict; while last["keep"] is true, fwd_bwd leaves its outputs and losses in it."""
     batch12 = (None, None, b["speakers"], b["texts"], b["src_lens"], b["max_src_len"], b["mels"], b["mel_lens"],
                b["max_mel_len"], b["pitches"], b["energies"], b["durations"])
 
@@ -174,6 +196,8 @@ def make_step(model, loss_fn, opt, b, exchange):
         out = model(*batch12[2:])
         losses = loss_fn(batch12, out)
         losses[0].backward()
+        if last is not None and last["keep"]:
+            last["out"], last["losses"] = out, losses
         return losses[0].detach()
 
     def step():
@@ -184,6 +208,39 @@ def make_step(model, loss_fn, opt, b, exchange):
         return loss
 
     return step, fwd_bwd
+
+
+class TrainState:
+    """--dump-outputs: the training state as build() left it - fp32 master weights, Adam moments and step counters, BatchNorm
+    statistics, dropout position - kept aside and put back right before the last timed step, outside the timing, so that the
+    dumped step computes from the same inputs in every run.  Without it the runs drift apart step by step: the float atomics of
+    some gradient kernels round differently from run to run, and Adam turns a gradient that is zero up to rounding into a
+    full-size update of either sign."""
+
+    def __init__(self, model, opt):
+        eng = model._engine
+        self.model, self.opt = model, opt
+        self.flat = model.flat_parameters().clone()
+        self.m, self.v = opt._m.clone(), opt._v.clone()
+        self.buffers = {n: t.clone() for n, t in model.named_buffers()}
+        self.steps = (opt.current_step, opt._adam_step)
+        self.seed = (eng._seed_k, eng.seed_counter.clone())
+
+    def restore(self):
+        from fastspeech2_amd import ops
+        model, opt, eng = self.model, self.opt, self.model._engine
+        model.flat_parameters().copy_(self.flat)
+        opt._m.copy_(self.m)
+        opt._v.copy_(self.v)
+        for n, t in model.named_buffers():
+            t.copy_(self.buffers[n])
+        opt.current_step, opt._adam_step = self.steps
+        eng._seed_k = self.seed[0]
+        eng.seed_counter.copy_(self.seed[1])
+        lp = eng.lowp_buffer()
+        if lp is not None:
+            ops.cast(model.flat_parameters(), eng.cdt, out=lp)     # the bf16 shadow, as the Adam pass leaves it
+        model._invalidate(lowp_synced=lp is not None)
 
 
 def capture_graph(model, opt, fwd_bwd, fork=False):
@@ -221,6 +278,50 @@ def capture_graph(model, opt, fwd_bwd, fork=False):
         graph.replay()
 
     return graph, static_loss, replay
+
+
+# --dump-outputs: element caps of the arrays that can be large (4 bytes each; < 64 MB in all with the small ones)
+DUMP_CAP = {"mel_prediction": 6 << 20, "postnet_mel_prediction": 6 << 20, "parameters": 2 << 20}
+
+
+def _sample(t, cap, seed):
+    """t itself, or - when it holds more than `cap` elements - `cap` of them at fixed seeded positions (ascending, flattened)"""
+    t = t.detach()
+    if t.numel() <= cap:
+        return t
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def write_outputs(dirname, arrays):
+    """{name: tensor} -> dirname/<name>.npy, float64 kept, everything else as float32"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
+def train_outputs(model, last):
+    """what a caller of the train step receives from its last run: the losses (total, mel, postnet mel, pitch, energy,
+    duration), the forward outputs and the parameters after the update (a fixed sample of the flat fp32 buffer)"""
+    out, losses = last["out"], last["losses"]
+    arrays = {"losses": torch.cat([l.detach().double().reshape(-1) for l in losses])}
+    for i, name in enumerate(("mel_prediction", "postnet_mel_prediction", "pitch_prediction", "energy_prediction",
+                              "log_duration_prediction", "duration_rounded")):
+        arrays[name] = _sample(out[i], DUMP_CAP[name], i) if name in DUMP_CAP else out[i]
+    arrays["mel_lens"] = out[9]
+    arrays["parameters"] = _sample(model.flat_parameters(), DUMP_CAP["parameters"], 1234)
+    return arrays
+
+
+def synth_outputs(last):
+    """the last synthesised batch: int16 PCM of its utterances one after the other, their lengths, the postnet mel"""
+    out, wavs = last["out"], last["wavs"]
+    return {"pcm": torch.cat([torch.as_tensor(w).reshape(-1).float() for w in wavs]),
+            "pcm_lens": torch.tensor([len(w) for w in wavs]), "postnet_mel_prediction": out[1], "mel_lens": out[9]}
 
 
 def _thread_counts(args):
@@ -332,14 +433,14 @@ SYNTH_NAMES = {1: "conv_gemm_kernel", 2: "conv_gemm_dma_kernel", 3: "conv_gemm_r
                10: "resblock_fused_kernel (HiFi-GAN C = 32 / 64: a stage's three residual blocks in one launch)"}
 
 
-def synth_measure(args, device, rank, world, steps, warmup, want_roofline):
+def synth_measure(args, device, rank, world, steps, warmup, want_roofline, dump_dir=None):
     """BASELINE metric part 2: batch-synthesis real-time factor = wall(acoustic model + HiFi-GAN + int16 + PCM to host) / audio
     seconds.  Workload = the reference's `synthesize.py --mode batch --source val.txt` (synthesize.py:197-199): the 512
     utterances of LJSpeech val.txt in FILE ORDER, 8 per batch, unsorted, each batch padded to its own longest utterance - the
     phoneme counts are the real ones (fastspeech2_amd/workloads/ljspeech_val_phonemes.json, made from the reference by
     tools/make_val_shape.py), the phoneme ids are random, weights are random-init with the duration predictor's bias set so that
     ~7 frames per phoneme come out.  A step = one batch of 8; with N ranks the 64 batches are dealt round-robin (replicas only).
-    Returns a dict of raw numbers (this rank's)."""
+    Returns a dict of raw numbers (this rank's).  dump_dir: the last timed batch's outputs go there (write_outputs)."""
     import math
     from fastspeech2_amd import synthetic as configs
     from fastspeech2_amd.synthetic import synthetic_batch, val_phoneme_counts
@@ -377,13 +478,18 @@ def synth_measure(args, device, rank, world, steps, warmup, want_roofline):
     # vocoder on another, PCM to the host behind an event; --no-synth-pipeline: the reference's sequential loop (A/B)
     pipe = None if args.no_synth_pipeline else utils.SynthPipeline(model, voc, (pcfg, mcfg), device=device, voc_streams=args.synth_voc_streams)
 
-    def run(n):
+    def run(n, last=None):
         """n batches through the loop under test; yields each batch's host PCM list (in order)"""
         if pipe is None:
             for i in range(n):
-                yield step(i)[1]
+                out, wavs = step(i)
+                if last is not None:
+                    last["out"], last["wavs"] = out, wavs
+                yield wavs
         else:
-            for _batch, _out, wavs in pipe(batches[i % len(batches)] for i in range(n)):
+            for _batch, out, wavs in pipe(batches[i % len(batches)] for i in range(n)):
+                if last is not None:
+                    last["out"], last["wavs"] = out, wavs
                 yield wavs
 
     for _ in run(warmup):
@@ -393,14 +499,18 @@ def synth_measure(args, device, rank, world, steps, warmup, want_roofline):
         dist.barrier()
     torch.cuda.synchronize()
     audio_samples, frames = 0, 0
+    last = {} if dump_dir else None
     t0 = time.perf_counter()
-    for wavs in run(steps):                                     # (fill and drain of the pipeline are inside the timed region)
+    for wavs in run(steps, last):                               # (fill and drain of the pipeline are inside the timed region)
         audio_samples += sum(len(w) for w in wavs)            # (host lists: the PCM is already on the host)
         frames += int(sum(len(w) for w in wavs)) // 256
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if last is not None:
+        write_outputs(dump_dir, synth_outputs(last))
+        del last
     res = {"dt": dt, "audio_s": audio_samples / 22050.0, "frames": float(frames), "n_batches": len(batches),
            "first_batch": groups[0],
            "loop": "sequential (synthesize.py:87-103)" if pipe is None else
@@ -453,7 +563,8 @@ def synth_main(args):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     import torch.distributed as dist
     device = init_rank(world, local_rank)
-    r = synth_measure(args, device, rank, world, args.steps, args.warmup, rank == 0 and not args.no_roofline)
+    r = synth_measure(args, device, rank, world, args.steps, args.warmup, rank == 0 and not args.no_roofline,
+                      args.dump_outputs if rank == 0 else None)
     tt = torch.tensor([r["dt"], r["audio_s"], r["frames"]], device=device, dtype=torch.float64)
     if world > 1:
         tmax = tt[:1].clone()
@@ -580,46 +691,68 @@ def main():
         exchange = ddp.GradExchange(model.flat_gradients(), world)
         model._engine.grad_hook = exchange.ready
         dist.broadcast(model.flat_parameters(), 0)
-    step, fwd_bwd = make_step(model, loss_fn, opt, b, exchange)
+    # --dump-outputs: the last timed step's results (kept on rank 0), computed from the initial state on every rank (TrainState)
+    last = {"keep": False} if args.dump_outputs else None
+    initial = TrainState(model, opt) if last is not None else None
+    step, fwd_bwd = make_step(model, loss_fn, opt, b, exchange, last if rank == 0 else None)
 
     use_graph = bool(args.graph) and not pg
     graph = None
     if use_graph:
         model._engine.device_seed = True         # dropout position in device memory from the first warm-up step on
+    loss = None
     for _ in range(max(args.warmup, 3) if use_graph else args.warmup):
         loss = step()
     torch.cuda.synchronize()
     replay = None
     if use_graph:
+        if last is not None:
+            last["keep"] = True                  # the captured outputs are static tensors: every replay refills them
         try:
             graph, static_loss, replay = capture_graph(model, opt, fwd_bwd)
         except Exception as e:  # capture is an optimisation, never a change of what is computed
             print(f"[bench] hipGraph capture failed ({type(e).__name__}: {e}); running eager", file=sys.stderr)
             graph = None
             torch.cuda.synchronize()
+        if last is not None:
+            last["keep"] = False
 
     def run_step():
         if graph is not None:
             replay()
         else:
-            step()
+            return step()
 
     for _ in range(2):
-        run_step()
-    # the timed region (EXACTLY --steps steps between barrier + synchronize on both sides) is repeated --windows times and the
-    # MEDIAN window is reported: one 20-step window is ~0.2 s, boxes differ by several per cent and clocks wander
+        settle_loss = run_step()
+    # the timed region (EXACTLY --steps steps between barrier + synchronize on both sides) is repeated --windows times (one by
+    # default, five with --full) and the MEDIAN window is reported: boxes differ by several per cent and clocks wander
     window_s = []
-    for _ in range(max(1, args.windows)):
+    n_windows = max(1, args.windows)
+    for w in range(n_windows):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for i in range(args.steps):
+            if last is not None and w == n_windows - 1 and i == args.steps - 1:
+                torch.cuda.synchronize()
+                paused = time.perf_counter()
+                initial.restore()
+                last["keep"] = True
+                torch.cuda.synchronize()
+                t0 += time.perf_counter() - paused      # (the restore is not part of the step)
             run_step()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         window_s.append(time.perf_counter() - t0)
+    if last is not None:
+        if rank == 0:
+            write_outputs(args.dump_outputs, train_outputs(model, last))
+        last.clear()
+        last["keep"] = False                     # (the --full measurements below run more steps)
+        del initial
     wt = torch.tensor(window_s, device=device, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(wt, op=dist.ReduceOp.MAX)              # per window: the slowest rank
@@ -639,21 +772,22 @@ def main():
     if pg:
         dist.all_reduce(frames)
         dist.all_reduce(padded)
-        # data-parallel sanity carried by the line itself: the group really has N ranks on this backend and, after the timed
-        # steps, every replica holds bit-identical parameters (each saw its own batch; only the exchanged gradients couple them)
+        # data-parallel sanity carried by the line itself: the group really has N ranks on this backend and (--full), after the
+        # timed steps, every replica holds bit-identical parameters (each saw its own batch; only the exchanged gradients couple them)
         assert dist.get_world_size() == world == args.gpus, (dist.get_world_size(), world, args.gpus)
-        chk = torch.stack([model.flat_parameters().double().sum(), model.flat_parameters().double().abs().sum()])
-        allchk = [torch.zeros_like(chk) for _ in range(world)]
-        dist.all_gather(allchk, chk)
         dist_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
-                     "replicas_bit_identical": all(torch.equal(c, allchk[0]) for c in allchk),
                      # what the exchange did in the last timed step: all_reduce calls launched by the engine's prefix hooks (under
                      # backward) and by finish() (after it), on the communication stream
                      "exchange": {"collectives_total": exchange.n_buckets, "last_step_under_backward": exchange.last_step[0],
                                   "last_step_in_finish": exchange.last_step[1], "flat_gradient_mb": round(exchange.n * 4 / 2 ** 20, 1)}}
+        if args.full:
+            chk = torch.stack([model.flat_parameters().double().sum(), model.flat_parameters().double().abs().sum()])
+            allchk = [torch.zeros_like(chk) for _ in range(world)]
+            dist.all_gather(allchk, chk)
+            dist_info["replicas_bit_identical"] = all(torch.equal(c, allchk[0]) for c in allchk)
     value = frames.item() * args.steps / dt
-    final_loss = float((static_loss if graph is not None else loss).item())
-    if pg:
+    final_loss = float((static_loss if graph is not None else loss if loss is not None else settle_loss).item())
+    if pg and args.full:
         # what each rank's OWN batch costs without the exchange (5 local steps; the replicas diverge from here on, nothing
         # below depends on them): the data-parallel step runs at the slowest rank's pace
         model._engine.grad_hook = None

@@ -7,9 +7,11 @@
 step_and_update_lr, zero_grad), writes `{dir}/2.pth.tar` = {"model", "optimizer"} exactly as train.py:152-161 does, then takes
 step 3 and returns its losses / learning rate / updated parameters.  A full checkpoint is ~70 MB (the PostNet's width is not
 configurable), so it is NOT committed: ckpt_resume.npz holds per-tensor checksums of the reference-written file (model, exp_avg,
-exp_avg_sq), the step-3 results and a few full tensors; tests/test_checkpoint_cpu.py (which runs where /root/reference exists)
-re-runs this function and loads the real file into the product, and the GPU test rebuilds the same file from the oracle +
-torch.optim.Adam, proves it against these checksums and resumes the product from it.
+exp_avg_sq), the step-3 results and a few full tensors; ckpt_reference.npz holds the file's layout (keys, shapes, dtypes,
+parameter order, optimiser groups and state) and a seeded sample of every tensor.  tests/test_checkpoint_cpu.py rebuilds the
+same file from the oracle + torch.optim.Adam, holds it to that layout and those samples and moves it between the product and
+the reference's model / optimiser layout; the GPU test proves the rebuilt file against the checksums and resumes the product
+from it.
 """
 import os
 import sys
@@ -25,6 +27,7 @@ from tests.golden import configs  # noqa: E402
 from oracle.weights import seeded_state_dict, synthetic_batch  # noqa: E402
 
 SEED, B, L = 606, 3, 14
+SAMPLE = 128                    # elements per tensor of the reference-written file kept in ckpt_reference.npz
 CFG = dict(dec_layers=2, enc_layers=2)
 FULL = ("mel_linear.bias", "decoder.layer_stack.1.pos_ffn.layer_norm.weight", "encoder.layer_stack.0.slf_attn.fc.bias",
         "variance_adaptor.pitch_predictor.linear_layer.weight", "postnet.convolutions.4.1.bias")
@@ -63,7 +66,7 @@ def reference_two_steps(out_dir):
         loss_fn = FastSpeech2Loss(pcfg, mcfg)
         opt = ScheduledOptim(model, configs.TRAIN, mcfg, 0)
         names = [n for n, _ in model.named_parameters()]
-        res = {}
+        res = {"requires_grad": [p.requires_grad for _, p in model.named_parameters()]}
         for step in (1, 2, 3):
             out = model(*batch12[2:])
             losses = loss_fn(batch12, out)
@@ -89,6 +92,39 @@ def reference_two_steps(out_dir):
         os.chdir(cwd)
 
 
+def reference_file_golden(ckpt, param_names, requires_grad, lr3, k=SAMPLE):
+    """ckpt_reference.npz: what tests/test_checkpoint_cpu.py needs of the reference-written `2.pth.tar` without the reference.
+    `layout` (JSON) = the file's model keys in order with shape / dtype, the reference's named_parameters() order with
+    requires_grad, the optimiser's param_groups and per-index state keys and steps, the non-float model tensors in full.
+    Every float tensor (model, exp_avg, exp_avg_sq) contributes its max |x| and `k` elements at seeded positions."""
+    import json
+    model = ckpt["model"]
+    groups = [{key: (list(v) if isinstance(v, tuple) else (float(v) if isinstance(v, np.floating) else v))
+               for key, v in g.items()} for g in ckpt["optimizer"]["param_groups"]]
+    state = {str(i): {"keys": sorted(st), "step": float(st["step"]), "step_dtype": str(st["step"].dtype)}
+             for i, st in ckpt["optimizer"]["state"].items()}
+    layout = {"model": [[key, list(v.shape), str(v.dtype)] for key, v in model.items()],
+              "param_names": list(param_names), "requires_grad": list(requires_grad), "param_groups": groups, "state": state,
+              "model_int": {key: v.tolist() for key, v in model.items() if not v.is_floating_point()}, "lr3": lr3}
+    tensors = {"model:" + key: v for key, v in model.items() if v.is_floating_point()}
+    for i, st in ckpt["optimizer"]["state"].items():
+        tensors["exp_avg:" + param_names[int(i)]] = st["exp_avg"]
+        tensors["exp_avg_sq:" + param_names[int(i)]] = st["exp_avg_sq"]
+    rng = np.random.default_rng(SEED)
+    keys = sorted(tensors)
+    offsets, index, value, maxabs = [0], [], [], []
+    for key in keys:
+        flat = tensors[key].detach().reshape(-1).numpy()
+        idx = np.arange(flat.size) if flat.size <= k else np.sort(rng.choice(flat.size, k, replace=False))
+        index.append(idx.astype(np.int64))
+        value.append(flat[idx].astype(np.float32))
+        offsets.append(offsets[-1] + idx.size)
+        maxabs.append(float(np.abs(flat).max()))
+    np.savez_compressed(os.path.join(HERE, "ckpt_reference.npz"), layout=np.array(json.dumps(layout)), keys=np.array(keys),
+                        offsets=np.array(offsets, dtype=np.int64), index=np.concatenate(index), value=np.concatenate(value),
+                        maxabs=np.array(maxabs))
+
+
 if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as d:
@@ -104,4 +140,5 @@ if __name__ == "__main__":
         np.savez_compressed(os.path.join(HERE, "ckpt_resume.npz"), keys=np.array(keys), stats=np.array([stats[k] for k in keys]),
                             losses3=r["losses3"], lr3=r["lr3"], adam_step=float(st0["step"]),
                             lr_in_ckpt=float(ckpt["optimizer"]["param_groups"][0]["lr"]), torch_version=torch.__version__, **extra)
+        reference_file_golden(ckpt, r["param_names"], r["requires_grad"], r["lr3"])
         print("ckpt", os.path.getsize(r["path"]) >> 20, "MB;", len(keys), "tensors; losses3", r["losses3"], "lr3", r["lr3"])

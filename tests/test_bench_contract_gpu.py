@@ -1,9 +1,12 @@
-"""bench.py's output contract (GPU): ONE JSON line with the metric BASELINE.json names, whole-job value, the roofline object
-(dominant kernel, live HIP-event timing, algorithmic FLOPs) and the cpu_baseline object (oracle on the host cores)."""
+"""bench.py's output contract (GPU): ONE JSON line with the metric BASELINE.json names and the whole-job value; with --full also
+the roofline object (dominant kernel, live HIP-event timing, algorithmic FLOPs) and the cpu_baseline object (oracle on the host
+cores).  A plain run times exactly --steps steps and can write the last step's outputs (--dump-outputs)."""
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
 
 import pytest
 
@@ -19,7 +22,7 @@ def _clean_env(**extra):
 
 
 def test_bench_line_contract(dev):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=_clean_env())
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
@@ -72,6 +75,43 @@ def test_bench_line_contract(dev):
     assert sc["kind"] == "port" and sc["value"] > 10 * sy["rtf"] and sc["cores"] >= 1
 
 
+def test_bench_plain_run_times_steps_and_dumps_outputs(dev, tmp_path):
+    """the plain run: one window of exactly --steps steps, nothing measured beside it, the last step's outputs on request -
+    the same from run to run"""
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=_clean_env())
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("mel-frames/sec") and d["unit"] == "mel-frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["steps"] == 4 and d["warmup"] == 2 and d["roofline"] is None and d["cpu_baseline"] is None
+    cfg = d["config"]
+    assert cfg["windows"] == 1 and cfg["window_ms_per_step"] == [d["ms_per_step"]]
+    assert "synth" not in cfg and "fp32_ms_per_step" not in cfg and "hip_graph_ms_per_step" not in cfg
+    frames_per_step = d["value"] * d["ms_per_step"] * 1e-3
+    assert 0.75 * 48 * 925 < frames_per_step <= 48 * 925 * 1.001, frames_per_step
+    files = sorted(os.listdir(dump))
+    assert {"losses.npy", "mel_prediction.npy", "postnet_mel_prediction.npy", "parameters.npy"} <= set(files), files
+    assert sum(os.path.getsize(dump / f) for f in files) < 64 << 20
+    arrays = {f: np.load(dump / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    losses = arrays["losses.npy"]
+    assert losses.shape == (6,) and np.isfinite(losses).all() and abs(losses[0] - losses[1:].sum()) < 1e-3 * abs(losses[0])
+    mel, lens = arrays["postnet_mel_prediction.npy"], arrays["mel_lens.npy"]
+    assert mel.shape[0] == 48 and mel.shape[2] == 80 and lens.shape == (48,) and mel.shape[1] == lens.max()
+    assert abs(lens.sum() - frames_per_step) <= 1e-3 * frames_per_step and np.isfinite(mel).all()
+    # the dumped step starts from the seeded initial state: another run, with other step counts, dumps the same step to rounding
+    dump2 = tmp_path / "outputs2"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "0",
+                          "--dump-outputs", str(dump2)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=_clean_env())
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert sorted(os.listdir(dump2)) == files
+    for f in files:
+        assert np.allclose(np.load(dump2 / f), arrays[f], rtol=1e-5, atol=1e-6), f
+
+
 def test_bench_refuses_development_switches(dev):
     env = dict(os.environ, FS2_GEMM_ABL="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"], capture_output=True, text=True,
@@ -81,7 +121,7 @@ def test_bench_refuses_development_switches(dev):
 
 def test_bench_synth_line_has_roofline(dev):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "synth", "--steps", "16", "--warmup", "16",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.strip().split("\n") if l.startswith("{")][0])
     assert d["higher_is_better"] is False and d["value"] > 0 and d["steps"] == 16 and "val.txt" in d["config"]["workload"]
@@ -96,7 +136,7 @@ def test_bench_two_ranks_shared_gpu(dev):
     exchange hooks, global loss counts, barrier + max-over-ranks timing, rank 0's local roofline replay, joint exit — as shipped."""
     env = _clean_env(FS2_BENCH_BACKEND="gloo", FS2_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
@@ -129,7 +169,7 @@ def test_bench_two_ranks_libritts_buckets_differ(dev):
     env = dict(os.environ, FS2_BENCH_BACKEND="gloo", FS2_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29519", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "libritts",
-           "--no-roofline"]
+           "--full", "--no-roofline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.strip().split("\n") if l.startswith("{")][0])

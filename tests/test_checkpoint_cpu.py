@@ -1,9 +1,12 @@
 """(f)3 released-checkpoint compatibility, host side (reference train.py:152-161, utils/model.py:15-28, model/optimizer.py:19-31).
 
-Runs where /root/reference exists (the build container): the LIVE reference writes `2.pth.tar` after two optimiser steps; the
-product restores it through get_model(--restore_step 2) - weights, Adam moments, step counters, learning-rate schedule - and the
-product's own checkpoint loads back into the reference's model and torch.optim.Adam.  Also pins the oracle-written stand-in the
-GPU resume test uses (tests/helpers.oracle_written_checkpoint) to the reference-written file, tensor by tensor."""
+The file the reference's train loop writes after two optimiser steps (`2.pth.tar`) is rebuilt from the oracle + torch.optim.Adam
+(tests/helpers.oracle_written_checkpoint) and held to what tests/golden/ckpt_reference.npz keeps of the reference-written one:
+its layout (model keys, shapes and dtypes in file order, the reference model's parameters() order, the optimiser's param_groups
+and per-parameter state) and a seeded sample of every tensor (tests/golden/make_golden_ckpt.py).  The product restores that
+file through get_model(--restore_step 2) - weights, Adam moments, step counters, learning-rate schedule - and the product's own
+checkpoint loads back into the reference's model layout and a torch.optim.Adam built as the reference's ScheduledOptim builds it."""
+import json
 import os
 import sys
 import types
@@ -13,31 +16,63 @@ import pytest
 import torch
 
 from tests.golden import configs
-from tests.helpers import load_golden, oracle_written_checkpoint
+from tests.helpers import CKPT_CFG, load_golden, oracle_written_checkpoint
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the live reference at /root/reference")
+
+def _reference_file():
+    """(layout, {tensor key: (flat positions, values, max |x|)}) of the reference-written 2.pth.tar"""
+    g = load_golden("ckpt_reference")
+    layout = json.loads(str(g["layout"]))
+    off = g["offsets"]
+    samples = {str(k): (g["index"][off[i]:off[i + 1]], g["value"][off[i]:off[i + 1]], float(g["maxabs"][i]))
+               for i, k in enumerate(g["keys"])}
+    return layout, samples
+
+
+def _plain(v):
+    return list(v) if isinstance(v, tuple) else (float(v) if isinstance(v, np.floating) else v)
+
+
+def _assert_reference_layout(ck, names, layout):
+    """the file has the reference-written file's layout: model keys / shapes / dtypes in order, parameters() order,
+    optimiser groups (every field) and state (keys and step per parameter index), non-float tensors exact"""
+    assert [[k, list(v.shape), str(v.dtype)] for k, v in ck["model"].items()] == layout["model"]
+    assert names == layout["param_names"]
+    groups = ck["optimizer"]["param_groups"]
+    assert len(groups) == len(layout["param_groups"])
+    for g, rg in zip(groups, layout["param_groups"]):
+        assert sorted(g) == sorted(rg)
+        for key, v in rg.items():
+            if key == "lr":
+                assert abs(float(g[key]) - v) <= 1e-12 * v
+            else:
+                assert _plain(g[key]) == v, key
+    st = ck["optimizer"]["state"]
+    assert sorted(str(i) for i in st) == sorted(layout["state"])
+    for i, s in st.items():
+        r = layout["state"][str(i)]
+        assert sorted(s) == r["keys"] and float(s["step"]) == r["step"] and str(s["step"].dtype) == r["step_dtype"]
+    for k, v in layout["model_int"].items():
+        assert ck["model"][k].tolist() == v, k
 
 
 @pytest.fixture(scope="module")
 def ref_run(tmp_path_factory):
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import make_golden_ckpt as G
     d = tmp_path_factory.mktemp("refckpt")
-    r = G.reference_two_steps(str(d))
-    r["dir"], r["G"] = str(d), G
-    return r
+    path = str(d / "2.pth.tar")
+    _, _, _, ck, names = oracle_written_checkpoint(path)
+    layout, samples = _reference_file()
+    return {"dir": str(d), "path": path, "ckpt": ck, "param_names": names, "layout": layout, "samples": samples}
 
 
 def _args(step):
     return types.SimpleNamespace(restore_step=step)
 
 
-@needs_ref
 def test_reference_written_checkpoint_restores_into_the_product(ref_run):
     from fastspeech2_amd.utils import get_model
-    pcfg, mcfg = configs.make(dropout=False, **ref_run["G"].CFG)
+    _assert_reference_layout(ref_run["ckpt"], ref_run["param_names"], ref_run["layout"])
+    pcfg, mcfg = configs.make(dropout=False, **CKPT_CFG)
     tcfg = dict(configs.TRAIN, path=dict(configs.TRAIN["path"], ckpt_path=ref_run["dir"]))
     dev = torch.device("cpu")
     model, opt = get_model(_args(2), (pcfg, mcfg, tcfg), dev, train=True)
@@ -59,15 +94,17 @@ def test_reference_written_checkpoint_restores_into_the_product(ref_run):
     assert n_state == sum(1 for p in params if p.requires_grad)
     # the schedule continues at step 3 with the reference's learning rate
     opt.current_step += 1
-    assert abs(opt.init_lr * opt._get_lr_scale() - ref_run["lr3"]) <= 1e-12 * ref_run["lr3"]
+    lr3 = ref_run["layout"]["lr3"]
+    assert abs(opt.init_lr * opt._get_lr_scale() - lr3) <= 1e-12 * lr3
 
 
-@needs_ref
 def test_product_checkpoint_loads_into_the_reference(ref_run, tmp_path):
-    """train.py:152-161 on the product side -> the reference's FastSpeech2.load_state_dict (strict) and torch.optim.Adam."""
+    """train.py:152-161 on the product side -> the reference's FastSpeech2.load_state_dict (strict: the same keys, each of the
+    reference's shape) and ScheduledOptim's torch.optim.Adam over the reference model's parameters() (load_state_dict validates
+    the groups and takes the state)."""
     from fastspeech2_amd.utils import get_model
-    G = ref_run["G"]
-    pcfg, mcfg = configs.make(dropout=False, **G.CFG)
+    layout = ref_run["layout"]
+    pcfg, mcfg = configs.make(dropout=False, **CKPT_CFG)
     tcfg = dict(configs.TRAIN, path=dict(configs.TRAIN["path"], ckpt_path=ref_run["dir"]))
     model, opt = get_model(_args(2), (pcfg, mcfg, tcfg), torch.device("cpu"), train=True)
     model._ensure_flat(torch.device("cpu"))
@@ -75,44 +112,43 @@ def test_product_checkpoint_loads_into_the_reference(ref_run, tmp_path):
     path = tmp_path / "2.pth.tar"
     torch.save({"model": model.state_dict(), "optimizer": opt.state_dict()}, path)
     ck = torch.load(path, map_location="cpu", weights_only=False)
-    cwd = os.getcwd()
-    os.chdir(REF)
-    try:
-        from model import ScheduledOptim
-        ref_model = G.MG.build_reference(pcfg, mcfg)
-        missing = ref_model.load_state_dict(ck["model"], strict=True)
-        assert not missing.missing_keys and not missing.unexpected_keys
-        ropt = ScheduledOptim(ref_model, configs.TRAIN, mcfg, 2)
-        ropt.load_state_dict(ck["optimizer"])                # utils/model.py:26 (torch.optim.Adam.load_state_dict validates the groups)
-    finally:
-        os.chdir(cwd)
+    ref_model = {k: (shape, getattr(torch, dtype.split(".")[-1])) for k, shape, dtype in layout["model"]}
+    assert sorted(ck["model"]) == sorted(ref_model)
+    for k, v in ck["model"].items():
+        assert list(v.shape) == ref_model[k][0], k
+    rg = layout["param_groups"][0]
+    ref_params = [torch.zeros(ref_model[n][0], dtype=ref_model[n][1], requires_grad=r)
+                  for n, r in zip(layout["param_names"], layout["requires_grad"])]
+    ropt = torch.optim.Adam(ref_params, betas=tuple(rg["betas"]), eps=rg["eps"], weight_decay=rg["weight_decay"])   # optimizer.py:9-15
+    ropt.load_state_dict(ck["optimizer"])                # utils/model.py:26 (torch.optim.Adam.load_state_dict validates the groups)
     orig = torch.load(ref_run["path"], map_location="cpu", weights_only=False)["optimizer"]["state"]
-    got = ropt._optimizer.state_dict()["state"]
+    got = ropt.state_dict()["state"]
     assert sorted(got) == sorted(orig)
     for i in orig:
         assert float(got[i]["step"]) == float(orig[i]["step"]) == 2.0
         assert torch.equal(got[i]["exp_avg"], orig[i]["exp_avg"]) and torch.equal(got[i]["exp_avg_sq"], orig[i]["exp_avg_sq"])
 
 
-@needs_ref
-def test_oracle_written_checkpoint_equals_reference_written(ref_run, tmp_path):
-    _, _, _, ock, names = oracle_written_checkpoint(str(tmp_path / "2.pth.tar"))
-    rck = torch.load(ref_run["path"], map_location="cpu", weights_only=False)
-    assert list(ock["model"]) == list(rck["model"]) and names == ref_run["param_names"]
-    for k, v in rck["model"].items():
-        if v.is_floating_point():
-            assert torch.allclose(ock["model"][k], v, rtol=1e-5, atol=1e-7), k
+def test_oracle_written_checkpoint_equals_reference_written(ref_run):
+    """the rebuilt file against the reference-written one: layout, every tensor at the sampled positions (model tensors to
+    rtol 1e-5 / atol 1e-7, Adam moments to 2e-4 of the reference tensor's max |x|), optimiser hyperparameters."""
+    ock, names, layout, samples = ref_run["ckpt"], ref_run["param_names"], ref_run["layout"], ref_run["samples"]
+    _assert_reference_layout(ock, names, layout)
+    tensors = {"model:" + k: v for k, v in ock["model"].items() if v.is_floating_point()}
+    for i, st in ock["optimizer"]["state"].items():
+        tensors["exp_avg:" + names[int(i)]] = st["exp_avg"]
+        tensors["exp_avg_sq:" + names[int(i)]] = st["exp_avg_sq"]
+    assert sorted(tensors) == sorted(samples)
+    for k, t in tensors.items():
+        idx, ref, scale = samples[k]
+        got = t.detach().reshape(-1)[torch.from_numpy(idx)]
+        ref = torch.from_numpy(ref)
+        if k.startswith("model:"):
+            assert torch.allclose(got, ref, rtol=1e-5, atol=1e-7), k
         else:
-            assert torch.equal(ock["model"][k], v), k
-    assert sorted(ock["optimizer"]["state"]) == sorted(rck["optimizer"]["state"])
-    for i, st in rck["optimizer"]["state"].items():
-        o = ock["optimizer"]["state"][i]
-        assert float(o["step"]) == float(st["step"])
-        for key in ("exp_avg", "exp_avg_sq"):
-            scale = st[key].abs().max().item()
-            assert (o[key] - st[key]).abs().max().item() <= 2e-4 * scale + 1e-12, (names[int(i)], key)
-    go, gr = ock["optimizer"]["param_groups"][0], rck["optimizer"]["param_groups"][0]
-    assert go["params"] == gr["params"] and abs(go["lr"] - gr["lr"]) <= 1e-12 * gr["lr"] and tuple(go["betas"]) == tuple(gr["betas"])
+            assert (got - ref).abs().max().item() <= 2e-4 * scale + 1e-12, k
+    go, gr = ock["optimizer"]["param_groups"][0], layout["param_groups"][0]
+    assert go["params"] == gr["params"] and abs(go["lr"] - gr["lr"]) <= 1e-12 * gr["lr"] and list(go["betas"]) == gr["betas"]
 
 
 def test_oracle_written_checkpoint_matches_reference_checksums(tmp_path):

@@ -26,7 +26,8 @@ def test_bench_two_ranks_on_rccl(dev):
     env.pop("FS2_BENCH_BACKEND", None)
     env.pop("FS2_BENCH_SHARE_GPU", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--windows", "2"]
+           "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--windows", "2",
+           "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.strip().split("\n") if l.startswith("{")][0])

@@ -5,6 +5,6 @@
 export TMPDIR=/tmp
 R=${1:-3}
 for r in $(seq 1 $R); do
-  FS2_LIB_PATH=fastspeech2_amd/libfs2hip_prev.so python bench.py --no-cpu-baseline --no-roofline --no-fp32 --no-synth --no-graph-line $2 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('previous build ', d['ms_per_step'], d['value'], d['config']['window_ms_per_step'], d['config']['library'])"
-  python bench.py --no-cpu-baseline --no-roofline --no-fp32 --no-synth --no-graph-line $2 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('current build  ', d['ms_per_step'], d['value'], d['config']['window_ms_per_step'], d['config']['library'])"
+  FS2_LIB_PATH=fastspeech2_amd/libfs2hip_prev.so python bench.py --windows 5 --no-cpu-baseline --no-roofline --no-fp32 --no-synth --no-graph-line $2 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('previous build ', d['ms_per_step'], d['value'], d['config']['window_ms_per_step'], d['config']['library'])"
+  python bench.py --windows 5 --no-cpu-baseline --no-roofline --no-fp32 --no-synth --no-graph-line $2 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('current build  ', d['ms_per_step'], d['value'], d['config']['window_ms_per_step'], d['config']['library'])"
 done
