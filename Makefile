@@ -33,8 +33,8 @@ clean:
 
 .PHONY: all clean
 
-# Development build: the same sources with -DFS2_DEV (environment-driven ablation / forced-variant switches compiled IN).
-# Never loaded by the product: tools/ scripts select it with FS2_LIB_PATH=fastspeech2_amd/libfs2hip_dev.so.
+# Development build: the same sources with -DFS2_DEV (instruments that only record and choose no path: the attention phase
+# stamps, fs2_dev_wave_map).  Never loaded by the product: tools/ scripts select it with FS2_LIB_PATH=fastspeech2_amd/libfs2hip_dev.so.
 DEVOBJ := build/obj_dev
 DEVOBJS := $(patsubst $(CSRC)/%.hip,$(DEVOBJ)/%.o,$(SRCS)) $(DEVOBJ)/fs2_api.o
 DEVLIB := fastspeech2_amd/libfs2hip_dev.so

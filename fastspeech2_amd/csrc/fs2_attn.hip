@@ -337,24 +337,13 @@ __device__ __forceinline__ void attn_store_row(bf16_t* rowp, const f32x16 (&acc)
     }
 }
 
-// Raised wave priority around the MFMA runs of the two-waves-per-SIMD kernels (MI355X_MICROARCH: +4-7 % on an attention loop; here the
-// forward 60.6 -> 58.8 us same process, tools/attn_prio.py): the wave that is in a matrix run is not held up by its partner's softmax VALU.
-// Dev builds can switch it off (fs2_dev_attn_prio).
-#ifdef FS2_DEV
-__device__ int fs2_attn_prio_on = 1;
-extern "C" int fs2_dev_attn_prio(int on) { return hipMemcpyToSymbol(HIP_SYMBOL(fs2_attn_prio_on), &on, sizeof(int)) == hipSuccess ? 0 : 1; }
-#define FS2_ATTN_PRIO_INIT() const bool fs2_prio = fs2_attn_prio_on != 0
-#define FS2_ATTN_PRIO(v) do { if (fs2_prio) { if (v) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); } } while (0)
-#else
-#define FS2_ATTN_PRIO_INIT() do {} while (0)
-#define FS2_ATTN_PRIO(v) __builtin_amdgcn_s_setprio(v)
-#endif
+// Raised wave priority (s_setprio) around the MFMA runs of the two-waves-per-SIMD kernels (MI355X_MICROARCH: +4-7 % on an attention
+// loop; here the forward 60.6 -> 58.8 us same process): the wave that is in a matrix run is not held up by its partner's softmax VALU.
 #define FS2_STAMP_KERNEL 0
 __global__ void __launch_bounds__(256, 2) attn_fwd_bf16_kernel(const bf16_t* __restrict__ qkv, long ld, bf16_t* __restrict__ ctx,
                                                                long ldo, float* __restrict__ lse,
                                                                const int32_t* __restrict__ lens, int S, int H, float scale) {
     __shared__ __attribute__((aligned(16))) unsigned char sKV[2][2][64 * 256];   // [buffer][K | V]
-    FS2_ATTN_PRIO_INIT();
     FS2_STAMP_INIT();
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fl = lane & 31, h2 = lane >> 5;
     int qt, h, b;
@@ -411,7 +400,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_bf16_kernel(const bf16_t* __r
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
         {
-            FS2_ATTN_PRIO(1);
+            __builtin_amdgcn_s_setprio(1);
             bf16x8 c0 = fa.rk(0, 0, 0), c1 = fa.rk(0, 1, 0);
 #pragma unroll
             for (int st = 0; st < 8; ++st) {
@@ -423,7 +412,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_bf16_kernel(const bf16_t* __r
                 __builtin_amdgcn_sched_barrier(0);
                 c0 = n0; c1 = n1;
             }
-            FS2_ATTN_PRIO(0);
+            __builtin_amdgcn_s_setprio(0);
         }
         // Softmax bookkeeping in the log2 domain (p = exp2(s * scale * log2 e - m): one fma + one v_exp_f32 per score), the
         // key-padding mask only on the sequence's last tile, and a LAZY running maximum: the accumulators are rescaled only
@@ -465,7 +454,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_bf16_kernel(const bf16_t* __r
         FS2_STAMP_AT(k0, 3);
         {   // P V: the four V fragments of the next 16-key group are fetched while the current group is multiplied
             bf16x8 cv[4], nv[4];
-            FS2_ATTN_PRIO(1);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) cv[nb] = fa.rt(1, 0, nb);
 #pragma unroll
@@ -485,7 +474,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_bf16_kernel(const bf16_t* __r
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb) cv[nb] = nv[nb];
             }
-            FS2_ATTN_PRIO(0);
+            __builtin_amdgcn_s_setprio(0);
         }
         FS2_STAMP_AT(k0, 4);
         if (more) {
@@ -515,175 +504,9 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_bf16_kernel(const bf16_t* __r
 // why dK/dV ran at 323 TF next to dQ's 724 TF.  The probability / score-gradient math is branch-free (invalid pairs are
 // multiplied by an exact 0), and the fragment reads of each MFMA run are issued together in front of it (sched_barrier
 // keeps the scheduler from sinking them back to their consumers).
-__global__ void __launch_bounds__(256, 1) attn_bwd_dkv_bf16_kernel(const bf16_t* __restrict__ qkv, long ld,
-                                                                   const bf16_t* __restrict__ dctx, long ldo,
-                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                   bf16_t* __restrict__ dqkv, const int32_t* __restrict__ lens,
-                                                                   int S, int H, float scale) {
-    __shared__ __attribute__((aligned(16))) unsigned char sQD[2][2][64 * 256];   // [buffer][Q | dO]
-    __shared__ __attribute__((aligned(16))) float sLD[2][2][64];                 // [buffer][lse | delta] of the tile's queries
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fl = lane & 31, h2 = lane >> 5;
-    const int kt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int len = lens ? min(lens[b], S) : S;
-    const size_t rowbase = (size_t)b * S;
-    const int kbase = kt * 128 + w * 32;
-    bf16_t* dK = dqkv + rowbase * ld + (size_t)H * DK + h * DK;
-    bf16_t* dV = dqkv + rowbase * ld + (size_t)2 * H * DK + h * DK;
-    if (kt * 128 >= len) {
-        for (int i = tid; i < 128 * 32; i += 256) {
-            int r = i >> 5, c = (i & 31) * 4;
-            if (kt * 128 + r < S) {
-                st4<bf16_t>(dK + (size_t)(kt * 128 + r) * ld + c, make_float4(0.f, 0.f, 0.f, 0.f));
-                st4<bf16_t>(dV + (size_t)(kt * 128 + r) * ld + c, make_float4(0.f, 0.f, 0.f, 0.f));
-            }
-        }
-        return;
-    }
-    const bf16_t* Q = qkv + rowbase * ld + h * DK;
-    const bf16_t* K = qkv + rowbase * ld + (size_t)H * DK + h * DK;
-    const bf16_t* V = qkv + rowbase * ld + (size_t)2 * H * DK + h * DK;
-    const bf16_t* dO = dctx + rowbase * ldo + h * DK;
-    const float* lse_b = lse + ((size_t)b * H + h) * S;
-    const float* del_b = delta + ((size_t)b * H + h) * S;
-    const int mykey = kbase + fl;
-    const float key_ok = mykey < len ? 1.f : 0.f;
-    bf16x8 kf[8], vf[8];
-    load_row_frags(kf, K + (size_t)min(mykey, S - 1) * ld, h2, mykey < S);
-    load_row_frags(vf, V + (size_t)min(mykey, S - 1) * ld, h2, mykey < S);
-    f32x16 dk[4], dv[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dk[nb][r] = 0.f; dv[nb][r] = 0.f; }
-
-    // threads 0..63 carry lse, 64..127 delta of query (tile start + tid & 63); a query >= len gets lse = +inf -> p = 0
-    const float* ld_src = tid < 64 ? lse_b : del_b;
-    // (lse travels in the log2 domain: p = exp2(s * scale * log2 e - lse * log2 e) is one fma + one v_exp_f32 per score)
-    const float sc2 = scale * 1.4426950408889634f;
-    auto load_ld = [&](int q0) -> float {
-        int q = q0 + (tid & 63);
-        float v = ld_src[min(q, S - 1)];
-        if (tid < 64) v *= 1.4426950408889634f;
-        if (q >= len) v = tid < 64 ? INFINITY : 0.f;
-        return v;
-    };
-
-    uint4 tq0, tq1, tq2, tq3, td0, td1, td2, td3;
-    float tl = 0.f;
-    TILE_LOAD_REGS(tq, Q, ld, 0, S - 1);
-    TILE_LOAD_REGS(td, dO, ldo, 0, S - 1);
-    if (tid < 128) tl = load_ld(0);
-    TILE_STORE_REGS(sQD[0][0], tq);
-    TILE_STORE_REGS(sQD[0][1], td);
-    if (tid < 128) sLD[0][tid >> 6][tid & 63] = tl;
-    __syncthreads();
-    int buf = 0;
-    for (int q0 = 0; q0 < len; q0 += 64, buf ^= 1) {
-        const bool more = q0 + 64 < len;
-        if (more) {
-            TILE_LOAD_REGS(tq, Q, ld, q0 + 64, S - 1);
-            TILE_LOAD_REGS(td, dO, ldo, q0 + 64, S - 1);
-            if (tid < 128) tl = load_ld(q0 + 64);
-        }
-        const unsigned char* sQ = sQD[buf][0];
-        const unsigned char* sdO = sQD[buf][1];
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-            if (q0 + qb * 32 >= len) break;
-            // ---- S^T = Q K^T and dP^T = dO V^T for 32 queries x my 32 keys, then dV += P^T dO and dK += dS^T Q.  The 32 LDS
-            // fragments of a query block travel in four batches of eight through TWO register sets, each batch requested one
-            // 8-MFMA run (256 cycles) ahead of its use.  r03m: with all 32 fragments requested up front (fq/fd/tO/tQ = 128
-            // registers next to the 64 of K/V, the 32 prefetch registers and the softmax values) the kernel needed ~350 vector
-            // registers; the compiler parked 96 of them in AGPRs and moved them with 337 v_accvgpr_read/write per 64 MFMAs -
-            // 40 % of the loop's instructions at ~5 issue cycles each.
-            const int rq = qb * 32 + fl;
-            bf16x8 fa[4], fb[4], ga[4], gb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { fa[i] = frag_k(sQ, rq, i, h2); fb[i] = frag_k(sdO, rq, i, h2); }
-            // this lane's 16 queries: rows crow(r, h2) = (r&3) + 8*(r>>2) + 4*h2 -> four float4 per array
-            float4 l4[4], d4[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                l4[g] = *reinterpret_cast<const float4*>(&sLD[buf][0][qb * 32 + 8 * g + 4 * h2]);
-                d4[g] = *reinterpret_cast<const float4*>(&sLD[buf][1][qb * 32 + 8 * g + 4 * h2]);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { ga[i] = frag_k(sQ, rq, 4 + i, h2); gb[i] = frag_k(sdO, rq, 4 + i, h2); }
-            __builtin_amdgcn_sched_barrier(0);
-            f32x16 s, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], kf[i], s, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[i], vf[i], dp, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) { fa[nb] = frag_t(sdO, qb * 32, nb, lane); fb[nb] = frag_t(sQ, qb * 32, nb, lane); }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[i], kf[4 + i], s, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gb[i], vf[4 + i], dp, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) { ga[nb] = frag_t(sdO, qb * 32 + 16, nb, lane); gb[nb] = frag_t(sQ, qb * 32 + 16, nb, lane); }
-            __builtin_amdgcn_sched_barrier(0);
-            float pv[16], dsv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float lq = reinterpret_cast<const float*>(&l4[r >> 2])[r & 3];
-                const float dq_ = reinterpret_cast<const float*>(&d4[r >> 2])[r & 3];
-                const float p = __builtin_amdgcn_exp2f(fmaf(s[r], sc2, -lq)) * key_ok;   // lq = +inf for q >= len -> exp2(-inf) = 0
-                pv[r] = p;
-                dsv[r] = p * (dp[r] - dq_);                                  // (the softmax scale multiplies dK once, at the store)
-            }
-            {
-                const bf16x8 pa = pack8(pv), da = pack8(dsv);
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb) {
-                    dv[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, fa[nb], dv[nb], 0, 0, 0);
-                    dk[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, fb[nb], dk[nb], 0, 0, 0);
-                }
-            }
-            {
-                const bf16x8 pa = pack8(pv + 8), da = pack8(dsv + 8);
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb) {
-                    dv[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, ga[nb], dv[nb], 0, 0, 0);
-                    dk[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, gb[nb], dk[nb], 0, 0, 0);
-                }
-            }
-        }
-        if (more) {
-            TILE_STORE_REGS(sQD[buf ^ 1][0], tq);
-            TILE_STORE_REGS(sQD[buf ^ 1][1], td);
-            if (tid < 128) sLD[buf ^ 1][tid >> 6][tid & 63] = tl;
-        }
-        // the eight accumulators are pinned to the accumulation registers across the loop edge: left to itself the allocator carried
-        // them in VGPRs from one tile to the next and moved all 128 values into AGPRs and back around every tile's MFMAs
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) asm volatile("" : "+a"(dk[nb]), "+a"(dv[nb]));
-        __syncthreads();
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        int key = kbase + crow(r, h2);
-        if (key < S) {
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) {
-                dK[(size_t)key * ld + nb * 32 + fl] = f32_to_bf16(dk[nb][r] * scale);
-                dV[(size_t)key * ld + nb * 32 + fl] = f32_to_bf16(dv[nb][r]);
-            }
-        }
-    }
-}
-
-// ---- dK, dV, second form (round 6): the same tiles, fragments and arithmetic, SOFTWARE-PIPELINED inside the wave.
-// The first form runs one wave per SIMD (128 accumulator registers + 64 of K / V fragments leave no room for a second), and that
-// wave walked S^T / dP^T MFMAs -> exponentials -> dV / dK MFMAs strictly one after the other, each phase behind the LDS round
+// This is the second form (round 6): the first form's tiles, fragments and arithmetic, SOFTWARE-PIPELINED inside the wave.  The
+// first form (retired; git history has it) ran one wave per SIMD (128 accumulator registers + 64 of K / V fragments leave no room
+// for a second), and that wave walked S^T / dP^T MFMAs -> exponentials -> dV / dK MFMAs strictly one after the other, each phase behind the LDS round
 // trip of its fragments: 133 us per decoder layer at 17 % MFMA busy (r05zzz PMC) - 7 350 cycles per 64-query tile for 2 048 cycles
 // of MFMA.  Here the two 32-query blocks of a tile are skewed by one phase, so that every VALU phase has an independent MFMA run
 // to hide under and every fragment batch is requested one 8-MFMA run (256 cycles) before its use:
@@ -983,7 +806,6 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_bf16_kernel(const bf16_t* 
                                                                   bf16_t* __restrict__ dqkv, const int32_t* __restrict__ lens,
                                                                   int S, int H, float scale) {
     __shared__ __attribute__((aligned(16))) unsigned char sKV[2][2][64 * 256];   // [buffer][K | V]
-    FS2_ATTN_PRIO_INIT();
     FS2_STAMP_INIT();
     FS2_STAMP_RAW(0);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fl = lane & 31, h2 = lane >> 5;
@@ -1064,7 +886,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_bf16_kernel(const bf16_t* 
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
             {
-                FS2_ATTN_PRIO(1);
+                __builtin_amdgcn_s_setprio(1);
                 bf16x8 ck = fa.rk(0, kb, 0), cv = fa.rk(1, kb, 0);
 #pragma unroll
                 for (int st = 0; st < 8; ++st) {
@@ -1076,7 +898,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_bf16_kernel(const bf16_t* 
                     __builtin_amdgcn_sched_barrier(0);
                     ck = nk; cv = nv;
                 }
-                FS2_ATTN_PRIO(0);
+                __builtin_amdgcn_s_setprio(0);
             }
             FS2_STAMP_AT(k0 + 64, 2 + 3 * kb);
             float dsv[16];
@@ -1095,7 +917,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_bf16_kernel(const bf16_t* 
                 dsv[r] = p * (dp[r] - my_del);                                  // (the softmax scale multiplies dQ once, at the store)
             }
             FS2_STAMP_AT(k0 + 64, 3 + 3 * kb);
-            FS2_ATTN_PRIO(1);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 bf16x8 da = pack8(dsv + 8 * u);
@@ -1103,7 +925,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_bf16_kernel(const bf16_t* 
                 for (int nb = 0; nb < 4; ++nb)
                     dq[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa.rt(0, kb * 32 + 16 * u, nb), da, dq[nb], 0, 0, 0);       // dQ^T[d][q] += K^T dS^T
             }
-            FS2_ATTN_PRIO(0);
+            __builtin_amdgcn_s_setprio(0);
             FS2_STAMP_AT(k0 + 64, 4 + 3 * kb);
         }
         if (more) {
@@ -1380,9 +1202,7 @@ extern "C" int fs2_attn_bwd(const void* qkv, const void* ctx, const void* dctx, 
     } else if (dtype == FS2_BF16) {
         // dQ first: it also produces delta (row sums of dO * O) for the dK/dV kernel
         attn_bwd_dq_bf16_kernel<<<grid, 256, 0, stream>>>((const bf16_t*)qkv, ld, (const bf16_t*)ctx, (const bf16_t*)dctx, ldo, lse, delta, (bf16_t*)dqkv, lens, S, H, scale);
-        static const int dkv_form = fs2_dev_env("FS2_ATTN_DKV", 2);          // dev A/B: 1 = the phase-serial first form
-        if (dkv_form == 1) attn_bwd_dkv_bf16_kernel<<<grid, 256, 0, stream>>>((const bf16_t*)qkv, ld, (const bf16_t*)dctx, ldo, lse, delta, (bf16_t*)dqkv, lens, S, H, scale);
-        else attn_bwd_dkv2_bf16_kernel<<<grid, 256, 0, stream>>>((const bf16_t*)qkv, ld, (const bf16_t*)dctx, ldo, lse, delta, (bf16_t*)dqkv, lens, S, H, scale);
+        attn_bwd_dkv2_bf16_kernel<<<grid, 256, 0, stream>>>((const bf16_t*)qkv, ld, (const bf16_t*)dctx, ldo, lse, delta, (bf16_t*)dqkv, lens, S, H, scale);
     } else { fs2_set_error("attn_bwd: dtype"); return FS2_EDTYPE; }
     FS2_CHECK_LAUNCH("attn_bwd");
     return FS2_OK;

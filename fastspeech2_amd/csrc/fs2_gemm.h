@@ -26,7 +26,6 @@ struct ConvGemmArgs {
     float res_unlrelu;             // > 0: the residual operand R holds lrelu(r, slope) - use r > 0 ? r : r * res_unlrelu (= 1 / slope)
     float post_slope;              // > 0: the value stored is lrelu(v, post_slope), applied last (after residual, scale, accumulate)
     int vec_ok;                    // Y / R rows are 16-byte addressable (ld % elems-per-16B == 0, aligned bases)
-    int dbg;                       // dev ablations (FS2_GEMM_DBG): 1 = loaders issue no DMA, 2 = consumers issue no MFMA
 };
 
 // gemm_res_ln (N == 256: a workgroup owns whole rows): the epilogue of the projection IS the LayerNorm kernel

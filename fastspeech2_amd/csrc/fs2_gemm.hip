@@ -560,9 +560,7 @@ __device__ __forceinline__ void ring_loader(const ConvGemmArgs& a, unsigned char
         int n = min(n0 + r, a.N - 1);
         offB[j] = (unsigned)n * (unsigned)(a.ldw * 2) + (unsigned)((lc ^ ((r >> 1) & 7)) << 4);
     }
-    const bool nodma = FS2_DEV_DBG(a.dbg & 1);
     auto load_A = [&](int kc, int buf) {
-        if (nodma) return;
         const unsigned char* base = Xb + (size_t)kc * 128;
 #pragma unroll
         for (int j = 0; j < NJA; ++j) {
@@ -571,7 +569,6 @@ __device__ __forceinline__ void ring_loader(const ConvGemmArgs& a, unsigned char
         }
     };
     auto load_B = [&](int kc, int tap, int slot) {
-        if (nodma) return;
         const unsigned char* base = Wb + ((size_t)tap * a.Cin + (size_t)kc * 64) * 2;
         const unsigned d0 = smem_base + C::B_OFF + slot * RING_B_BYTES + lw * 4096;
 #pragma unroll
@@ -757,7 +754,6 @@ __global__ void __launch_bounds__(768, 3) conv_gemm_ring_kernel(ConvGemmArgs a) 
             return;
         }
     }
-    if (FS2_DEV_DBG(a.dbg & 16)) return;
     f32x16 acc[2][2];
     if (wave >= 8) {
         ring_loader<ONE_TAP>(a, smem, m0, n0, lane, wave - 8);
@@ -779,7 +775,6 @@ __global__ void __launch_bounds__(768, 3) conv_gemm_ring_kernel(ConvGemmArgs a) 
         }
     }
     __syncthreads();                                       // every consumer is done reading the operand slots
-    if (FS2_DEV_DBG(a.dbg & 8)) { if (tid == 0 && acc[0][0][0] == 12345.f) Y[0] = 0; return; }
 
     // epilogue: the whole 256x128 f32 tile through LDS (128 KB), written by the consumers, stored by all 8 waves
     float* tile = reinterpret_cast<float*>(smem);
@@ -804,7 +799,6 @@ __global__ void __launch_bounds__(768, 3) conv_gemm_ring_kernel(ConvGemmArgs a) 
         FS2_ACT_DISPATCH(a.act, stage(std::integral_constant<int, ACT>{}));
     }
     __syncthreads();
-    if (FS2_DEV_DBG(a.dbg & 32)) { if (tile[tid] == 12345.f) Y[0] = 0; return; }
     if (tid < 512) {                                       // (the shared store path walks 128 x 16 chunks in whole strides of its thread count)
         gemm_store_tile<bf16_t, 128, 512>(a, tile, m0, n0, tid);
         gemm_store_tile<bf16_t, 128, 512>(a, tile + 128 * 128, m0 + 128, n0, tid);
@@ -812,7 +806,7 @@ __global__ void __launch_bounds__(768, 3) conv_gemm_ring_kernel(ConvGemmArgs a) 
 }
 
 // =====================================================================================================
-// "Skinny" convolution: Cin == Cout == C in {32, 64, 128}, bf16 - the HiFi-GAN residual blocks after the first
+// "Skinny" convolution: Cin == Cout == C in {32, 64}, bf16 - the HiFi-GAN residual blocks after the first
 // upsampling stage (hifigan/models.py:96-103): M = B * T * up is huge (1.8 M rows per 8 utterances at the last stage),
 // C is tiny.  These layers are HBM-bound by construction (C=32, k=3: 48 FLOP per byte; every conv moves M*C*2 bytes in
 // and out = 236 MB at every stage), and the general kernels waste them: a 128x128 tile computes 4x / 2x more columns
@@ -824,13 +818,13 @@ __global__ void __launch_bounds__(768, 3) conv_gemm_ring_kernel(ConvGemmArgs a) 
 // accumulate, 1/3 scale) writes whole rows.  X is read once, Y written once: ~24 KB of HBM traffic per 128 rows.
 // LDS rows are C*2 bytes; 16-byte chunk c of row r is stored at chunk c ^ ((r / RPW) % CPR) (CPR = chunks per row,
 // RPW = rows per 256-byte bank window), which makes the ds_read_b128 of one chunk by 16 consecutive rows conflict-free
-// for all three widths.
+// for both widths.
 // (r01j: fusing a residual block's conv1 -> leaky-ReLU -> conv2 + residual into one kernel, intermediate in LDS, was tried
 // for C = 32 / 64: 2.5x less HBM traffic on paper, but two weight-group loops with a barrier pair per group (24 barriers at
 // k = 11) and 1-2 workgroups per CU made the synthesis step 24 % SLOWER than two skinny launches.  Not kept.)
 template <int C> struct SkinnyCfg {
     static constexpr int CPR = C / 8, RPW = 16 / CPR, XR_MAX = 192;
-    static constexpr int G = C == 32 ? 8 : (C == 64 ? 2 : 1);          // taps per weight group (16 / 16 / 32 KB)
+    static constexpr int G = C == 32 ? 8 : 2;                          // taps per weight group (16 / 16 KB)
     static constexpr int X_BYTES = XR_MAX * C * 2, W_BYTES = G * C * C * 2;
     static constexpr int EPI_BYTES = 128 * C * 4;
     static constexpr int LDS = (X_BYTES + W_BYTES) > EPI_BYTES ? (X_BYTES + W_BYTES) : EPI_BYTES;
@@ -894,7 +888,7 @@ __global__ void __launch_bounds__(256) conv_skinny_kernel(ConvGemmArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
 
-    constexpr int WI = (K::G * C * CPR) / 256;              // 16-byte chunks of a weight group per thread (4 / 4 / 8)
+    constexpr int WI = (K::G * C * CPR) / 256;              // 16-byte chunks of a weight group per thread (4 / 4)
     for (int g0 = 0; g0 < a.taps; g0 += K::G) {
         __syncthreads();                                   // X tile visible / previous weight group consumed
 #pragma unroll
@@ -938,7 +932,7 @@ __global__ void __launch_bounds__(256) conv_skinny_kernel(ConvGemmArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rl = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                tile[rl * C + (C == 128 ? fs2_tile_col128<bf16_t>(cl) : cl)] = act_ct<ACT>(acc[nb][r] + bv, a.slope);
+                tile[rl * C + cl] = act_ct<ACT>(acc[nb][r] + bv, a.slope);
             }
         }
     };
@@ -959,8 +953,7 @@ bool fs2_conv_gemm_w_ok(const ConvGemmArgs& a, bool has_map, int dtype);
 void fs2_conv_gemm_w_launch(const ConvGemmArgs& a, const int32_t* tile_map, hipStream_t stream);
 // defined in fs2_gemm_p.hip
 bool fs2_conv_gemm_p_ok(const ConvGemmArgs& a, bool has_map, int dtype, int ks);
-void fs2_conv_gemm_p_launch(const ConvGemmArgs& a, const int32_t* tile_map, hipStream_t stream, int abl, int ks, float* ws,
-                            float* tail_ws);
+void fs2_conv_gemm_p_launch(const ConvGemmArgs& a, const int32_t* tile_map, hipStream_t stream, int ks, float* ws, float* tail_ws);
 
 // Which kernel a launch description dispatches to: a PURE function of the description (no state, no environment in the
 // shipped build), shared by fs2_conv_gemm and by the query entry point fs2_conv_gemm_variant that bench.py uses to attribute
@@ -974,27 +967,21 @@ static GemmPick conv_gemm_pick(const ConvGemmArgs& a, int dtype, bool has_map, b
     GemmPick p;
     const long grid = (long)fs2_cdiv(M, 128) * fs2_cdiv(N, 128);
     // taps == 1 keeps the register-staged kernel (its 3-stage pipeline wins when there is no halo to reuse)
-    static const int dma1 = fs2_dev_env("FS2_GEMM_DMA1", 1);            // dev A/B: one-tap launches of few tiles and K >= 768 on the DMA kernel's in-workgroup K split
-    const bool dma = in_act == FS2_ACT_NONE && (taps > 1 || (dma1 && grid <= 160 && Cin % 128 == 0 && Cin >= 768 && dtype == FS2_BF16)) && (taps - 1) * dil <= 16 && taps <= 32;
-    // ring-buffered 256x128 tiles once there are enough of them to fill the chip (FS2_GEMM_TILE=128|256: dev A/B only)
-    static const int force_tile = fs2_dev_env("FS2_GEMM_TILE", 0);
+    // except one-tap launches of few tiles and K >= 768, which take the DMA kernel's in-workgroup K split
+    const bool dma = in_act == FS2_ACT_NONE && (taps > 1 || (grid <= 160 && Cin % 128 == 0 && Cin >= 768 && dtype == FS2_BF16)) && (taps - 1) * dil <= 16 && taps <= 32;
+    // ring-buffered 256x128 tiles once there are enough of them to fill the chip
     const long big_tiles = (long)fs2_cdiv(M, 256) * fs2_cdiv(N, 128);
     p.ring_inact = in_act == FS2_ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f;
     const bool ring_ok = dtype == FS2_BF16 && (in_act == FS2_ACT_NONE || p.ring_inact) && (taps == 1 || (taps >= 3 && (taps - 1) * dil <= 16 && taps <= 32)) &&
                          Cin % 64 == 0 && (double)M * a.ldx * 2 < 2.0e9 && (double)N * taps * Cin * 2 < 2.0e9;
     // taps == 1 contractions with a short K (4-12 steps) do not amortise the ring's fill: measured faster on the 128^2 kernel
-    bool big = ring_ok && big_tiles >= 170 && (taps > 1 || Cin >= 1024);
-    if (force_tile == 128) big = false;
-    if (force_tile == 256 && ring_ok) big = true;
+    const bool big = ring_ok && big_tiles >= 170 && (taps > 1 || Cin >= 1024);
     // C = 128 stays on the 256x128 / 128^2 kernels: it is MFMA-bound there (k=11: 172 GFLOP per conv) and one tap per
-    // weight group leaves only 32 MFMAs per wave between barriers (r01j A/B: 13.1 ms with, 12.0 ms without bit 4|8)
-    static const int skinny_mask = fs2_dev_env("FS2_GEMM_SKINNY", 3);    // dev A/B bits
-    const int skinny_bit = Cin == 32 ? 1 : (Cin == 64 ? 2 : (in_act == FS2_ACT_NONE ? 4 : 8));
-    const bool skinny = (skinny_mask & skinny_bit) && dtype == FS2_BF16 && N == Cin && (Cin == 32 || Cin == 64 || Cin == 128) && taps <= 16 &&
+    // weight group leaves only 32 MFMAs per wave between barriers (r01j A/B: 13.1 ms with, 12.0 ms without a C = 128 skinny kernel)
+    const bool skinny = dtype == FS2_BF16 && N == Cin && (Cin == 32 || Cin == 64) && taps <= 16 &&
                         (taps - 1) * dil <= 64 && (in_act == FS2_ACT_NONE || in_act == FS2_ACT_LRELU) && a.vec_ok;
     // persistent 256x128 kernel (fs2_gemm_p.hip): every shape the ring kernel takes plus the short-K one-tap contractions
-    // (its run-ahead loaders hide the per-tile ring fill those could not amortise).  FS2_GEMM_P=0: dev A/B against the ring.
-    static const int p_on = fs2_dev_env("FS2_GEMM_P", 1);
+    // (its run-ahead loaders hide the per-tile ring fill those could not amortise)
     // HiFi-GAN's stored-leaky-ReLU chain launches WITH a residual / accumulate operand and a short reduction (conv2 of a block: 6 - 44
     // K-steps): the ring kernel's LDS-staged epilogue reads the operand four chunks at a time, the persistent kernel's register
     // epilogue one chunk at a time behind its own stores (a vmcnt(0) each) - same box, `tools/bench_voc.py`: 116.7 -> 97.2 us (C = 128,
@@ -1002,17 +989,14 @@ static GemmPick conv_gemm_pick(const ConvGemmArgs& a, int dtype, bool has_map, b
     // at every shape (profiles/r05t_bench_voc_ring.log).  Scoped to the launches it was measured on.
     const bool res_short = (a.res_unlrelu > 0.f || a.post_slope > 0.f) && (a.R || a.accumulate) && a.act != FS2_ACT_GATE &&
                            (long)taps * ((Cin + 63) / 64) <= 48 && big;
-    const bool persist = p_on && !skinny && !res_short && fs2_conv_gemm_p_ok(a, has_map, dtype, 1) && (taps > 1 || Cin >= 256);
-    // few tiles, long reduction: split the Cin chunks over two wave groups of one workgroup (FS2_GEMM_KSPLIT=0: off)
-    static const int ksplit_on = fs2_dev_env("FS2_GEMM_KSPLIT", 1);
-    static const int ks2_min = fs2_dev_env("FS2_GEMM_KS2_MIN", 12);
-    p.ks2 = ksplit_on && dtype == FS2_BF16 && grid <= 160 && Cin % 128 == 0 && (long)taps * (Cin / 64) >= ks2_min;
-    // wide-tile one-tap kernel (fs2_gemm_w.hip): N a multiple of 256 - the Linear layers of the FFT blocks and their data gradients
-    static const int w_on = fs2_dev_env("FS2_GEMM_W", 1);
+    const bool persist = !skinny && !res_short && fs2_conv_gemm_p_ok(a, has_map, dtype, 1) && (taps > 1 || Cin >= 256);
+    // few tiles, long reduction (12 K-steps or more): split the Cin chunks over two wave groups of one workgroup
+    p.ks2 = dtype == FS2_BF16 && grid <= 160 && Cin % 128 == 0 && (long)taps * (Cin / 64) >= 12;
     // streaming kernel with the weights in registers (fs2_gemm_s.hip): the K = 256 Linear layers and data gradients
     const bool lrelu_io = a.res_unlrelu > 0.f || a.post_slope > 0.f;     // (the streaming kernel's own epilogue does not carry them)
     if (!skinny && !lrelu_io && fs2_conv_gemm_s_ok(a, dtype)) { p.variant = FS2_GEMM_STREAM_K256; return p; }
-    if (w_on && !skinny && fs2_conv_gemm_w_ok(a, has_map, dtype)) { p.variant = FS2_GEMM_WIDE_1TAP; return p; }
+    // wide-tile one-tap kernel (fs2_gemm_w.hip): N a multiple of 256 - the Linear layers of the FFT blocks and their data gradients
+    if (!skinny && fs2_conv_gemm_w_ok(a, has_map, dtype)) { p.variant = FS2_GEMM_WIDE_1TAP; return p; }
     p.variant = skinny ? FS2_GEMM_SKINNY : (persist ? (taps == 1 ? FS2_GEMM_PERSIST_1TAP : FS2_GEMM_PERSIST) : (big ? FS2_GEMM_RING : (dma ? FS2_GEMM_DMA : FS2_GEMM_PLAIN)));
     return p;
 }
@@ -1024,7 +1008,6 @@ static void conv_gemm_fill(ConvGemmArgs& a, const void* X, long ldx, const void*
     a.X = X; a.ldx = ldx; a.W = W; a.ldw = (long)taps * Cin; a.bias = bias; a.R = R; a.ldr = ldr; a.Y = Y; a.ldy = ldy;
     a.lens = lens; a.M = M; a.N = N; a.Cin = Cin; a.S = S; a.taps = taps; a.dil = dil; a.pad = pad; a.act = act;
     a.slope = slope; a.in_act = in_act; a.in_slope = in_slope; a.accumulate = accumulate; a.out_scale = out_scale;
-    a.dbg = 0;
     a.res_unlrelu = 0.f; a.post_slope = 0.f;
     a.vec_ok = (ldy % epc == 0) && (((uintptr_t)Y & 15) == 0) && (!R || ((ldr % epc == 0) && (((uintptr_t)R & 15) == 0)));
 }
@@ -1063,8 +1046,6 @@ static int conv_gemm_impl(const void* X, long ldx, const void* W, const float* b
     if (M == 0) return FS2_OK;
     ConvGemmArgs a;
     conv_gemm_fill(a, X, ldx, W, bias, R, ldr, Y, ldy, lens, M, N, Cin, S, taps, dil, pad, act, slope, in_act, in_slope, accumulate, out_scale, dtype);
-    static const int gemm_dbg = fs2_dev_env("FS2_GEMM_DBG", 0);
-    a.dbg = gemm_dbg;
     FS2_CHECK_ARG(res_unlrelu >= 0.f && post_slope >= 0.f && post_slope < 1.f && (res_unlrelu == 0.f || (R && act != FS2_ACT_GATE)),
                   "conv_gemm: res_unlrelu needs an additive residual operand, post_slope in [0, 1)");
     a.res_unlrelu = res_unlrelu; a.post_slope = post_slope;
@@ -1075,13 +1056,11 @@ static int conv_gemm_impl(const void* X, long ldx, const void* W, const float* b
         fs2_conv_gemm_s_launch(a, stream);
     } else if (pk.variant == FS2_GEMM_SKINNY) {
         if (Cin == 32) launch_skinny<32>(a, stream);
-        else if (Cin == 64) launch_skinny<64>(a, stream);
-        else launch_skinny<128>(a, stream);
+        else launch_skinny<64>(a, stream);
     } else if (pk.variant == FS2_GEMM_WIDE_1TAP) {
         fs2_conv_gemm_w_launch(a, tile_map, stream);
     } else if (pk.variant == FS2_GEMM_PERSIST || pk.variant == FS2_GEMM_PERSIST_1TAP) {
-        static const int abl = fs2_dev_env("FS2_GEMM_ABL", 0);
-        fs2_conv_gemm_p_launch(a, tile_map, stream, abl, 1, nullptr, tail_ws);
+        fs2_conv_gemm_p_launch(a, tile_map, stream, 1, nullptr, tail_ws);
     } else if (pk.variant == FS2_GEMM_RING) {
         static Fs2DevOnce ring_once;
         const int dyn1 = RingCfg<true>::B_OFF + RingCfg<true>::D * RING_B_BYTES;
@@ -1162,7 +1141,7 @@ extern "C" int fs2_conv_gemm_splitk(const void* X, long ldx, const void* W, cons
     ConvGemmArgs a;
     conv_gemm_fill(a, X, ldx, W, bias, R, ldr, Y, ldy, lens, M, N, Cin, S, taps, dil, pad, act, slope, FS2_ACT_NONE, 0.f, 0, out_scale, dtype);
     FS2_CHECK_ARG(fs2_conv_gemm_p_ok(a, tile_map != nullptr, dtype, ksplit), "conv_gemm_splitk: shape not supported (M=%d N=%d Cin=%d taps=%d ksplit=%d)", M, N, Cin, taps, ksplit);
-    fs2_conv_gemm_p_launch(a, tile_map, stream, 0, ksplit, ws, nullptr);
+    fs2_conv_gemm_p_launch(a, tile_map, stream, ksplit, ws, nullptr);
     FS2_CHECK_LAUNCH("conv_gemm_splitk");
     return FS2_OK;
 }
@@ -1542,7 +1521,7 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, unsigned cha
     auto ktile = [&](auto bufc, int u) {
         constexpr int BUF = decltype(bufc)::value;
         constexpr int bufoff = BUF * (A_BYTES + X_BYTES);
-        const bool live = live_lds[BUF] && !FS2_DEV_DBG(a.dbg & 2);
+        const bool live = live_lds[BUF];
         if (live) read_frags(0, bufoff, 0);
         load_tile(std::integral_constant<int, BUF>{}, u + 2);
         if (live) {
@@ -1562,7 +1541,6 @@ __device__ __forceinline__ void wgrad_bf16_body(const WgradArgs& a, unsigned cha
         ktile(I0{}, u);
         if (u + 1 < uend) ktile(I1{}, u + 1);
     }
-    if (FS2_DEV_DBG(a.dbg & 1)) return;
     const int fl = lane & 31, fh = lane >> 5;
     // split-K: with a slab, this split's partial tile goes to its OWN copy of dW (plain stores, a half-wave writes 32 consecutive
     // c = one full 128-byte line per store) and wgrad_finalize_kernel sums the splits in a fixed order (bit-reproducible
@@ -1653,8 +1631,6 @@ template <int NT, int REM, int NW>
 static void launch_wgrad_bf16(WgradArgs a, int S_eff, int g3, hipStream_t stream, const WgradPlan* plan = nullptr) {
     a.S = S_eff;
     a.g3 = g3;
-    static const int dbg = fs2_dev_env("FS2_WGRAD_DBG", 0);
-    a.dbg = dbg;
     const int dyn = 2 * (64 * 256 + 72 * 256);
     static Fs2DevOnce once;
     once.run([&] { (void)hipFuncSetAttribute((const void*)conv_wgrad_bf16_kernel<NT, REM, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn); });
@@ -1672,18 +1648,11 @@ static void launch_wgrad_bf16(WgradArgs a, int S_eff, int g3, hipStream_t stream
     // workgroup pays ~10 us of prologue/epilogue, so the depth is bounded from both sides (r01h sweep, tools/bench_wgrad.py):
     //   short reductions (encoder, 96 K-tiles)  -> ~192 workgroups;  1-tap GEMMs (2 workgroups per CU) -> ~384;  else ~768;
     //   and at least 8 (1-tap) / 16 (few-tile conv) K-tiles per workgroup when the reduction is long.
-    static const int wg_env = fs2_dev_env("FS2_WGRAD_WGS", 0);
-    static const int ups_env = fs2_dev_env("FS2_WGRAD_MINUPS", 0);
-    // r02 same-box A/B of the WHOLE step (tools/ab_env.py): these launches run on the side stream next to the data-gradient
-    // chain, and fewer, longer workgroups disturb it less than the split depth that is fastest in isolation: tap-group kernels
-    // at 192 workgroups, one-tap at 192 (profiles/r02y_ab_env*.log)
-    int wg_target = units < 256 ? 192 : (NT == 1 ? 192 : (NW == 8 ? 192 : 768));
-    int min_ups = NT == 1 ? 8 : ((tiles <= 8 && units >= 512) ? 16 : 4);
-    if (wg_env) wg_target = wg_env;
-    static const int wg_env1 = fs2_dev_env("FS2_WGRAD_WGS1", 0), wg_env3 = fs2_dev_env("FS2_WGRAD_WGS3", 0);
-    if (NT == 1 && wg_env1) wg_target = wg_env1;
-    if (NT > 1 && wg_env3) wg_target = wg_env3;
-    if (ups_env) min_ups = ups_env;
+    // r02 same-box A/B of the WHOLE step: these launches run on the side stream next to the data-gradient chain, and fewer,
+    // longer workgroups disturb it less than the split depth that is fastest in isolation: tap-group kernels at 192 workgroups,
+    // one-tap at 192 (profiles/r02y_ab_env*.log)
+    const int wg_target = 192;
+    const int min_ups = NT == 1 ? 8 : ((tiles <= 8 && units >= 512) ? 16 : 4);
     long want = (NW == 8 && NT > 1) ? (wg_target / tiles) : (wg_target + tiles - 1) / tiles;   // floor: never spill into a second round
     if (want < 1) want = 1;
     long ups = (units + want - 1) / want;
@@ -1704,7 +1673,7 @@ static int conv_wgrad_impl(const void* dY, long lddy, const void* X, long ldx, f
     if (M == 0) return FS2_OK;
     WgradArgs a;
     a.dY = dY; a.lddy = lddy; a.X = X; a.ldx = ldx; a.dW = dW; a.dbias = dbias; a.lens = lens; a.M = M; a.N = N; a.Cin = Cin; a.S = S; a.taps = taps;
-    a.dil = dil; a.pad = pad; a.g3 = 0; a.dbg = 0; a.slab = nullptr; a.slab_stride = 0;
+    a.dil = dil; a.pad = pad; a.g3 = 0; a.slab = nullptr; a.slab_stride = 0;
     long tiles = (long)fs2_cdiv(N, 128) * fs2_cdiv(Cin, 128) * taps;
     // split rows so that ~1024 workgroups exist, each covering a multiple of 32 rows (>= 256 rows).
     long want = (1024 + tiles - 1) / tiles;
@@ -1718,33 +1687,28 @@ static int conv_wgrad_impl(const void* dY, long lddy, const void* X, long ldx, f
     if (dtype == FS2_F32) conv_wgrad_kernel<float><<<grid, 256, 0, stream>>>(a);
     else if (dtype == FS2_BF16) {
         bool fast = (N % 8 == 0) && (Cin % 8 == 0) && (lddy % 8 == 0) && (ldx % 8 == 0) && (((uintptr_t)dY | (uintptr_t)X) & 15) == 0;
-        static const int wg_waves = fs2_dev_env("FS2_WGRAD_WAVES", 8);   // dev A/B: 4 | 8
-        static const int wg_waves1 = fs2_dev_env("FS2_WGRAD_WAVES1", 4);            // dev A/B: 4 | 8
         const bool conv_ok = fast && taps > 1 && 2 * dil <= 8 && M % S == 0;
         const bool one_ok = fast && taps == 1;
         // slab split-K (round 3): needs the caller's workspace (fs2_conv_wgrad_ws_bytes) and 16-byte addressable gradients
-        static const int slab_env = fs2_dev_env("FS2_WGRAD_SLAB", 1);   // dev A/B: 0 = atomics even with a workspace
         WgradPlan plan = wgrad_plan(M, N, Cin, S, taps, dil, lens != nullptr, true);
         const long need = (long)plan.splits * ((long)N * taps * Cin + N) * 4;
         // One-tap (Linear) gradients stay on the atomic path: they are short HBM-bound launches whose split depth was tuned for
         // it, and with slabs they measured SLOWER on the first round-3 run (r03b: fc 28 -> 42 us, mel 19 -> 44, encoder shapes
         // 17-21 -> 22-23; only the K = 1024 FFN shape gained, 70 -> 62): 64-128 splits of a 64 KB tile turn the finalize pass into
-        // a latency chain.  one_slab (dev builds) re-enables it for A/B.
-        static const int one_slab = fs2_dev_env("FS2_WGRAD_SLAB1", 0);
-        const bool slab = slab_env && ws && ws_bytes >= need && ((one_ok && one_slab) || conv_ok) && (((uintptr_t)dW | (uintptr_t)dbias | (uintptr_t)ws) & 15) == 0 &&
+        // a latency chain.
+        const bool slab = ws && ws_bytes >= need && conv_ok && (((uintptr_t)dW | (uintptr_t)dbias | (uintptr_t)ws) & 15) == 0 &&
                           ((long)N * taps * Cin) % 4 == 0;
         if (slab) { a.slab = ws; a.slab_stride = (long)N * taps * Cin + N; }
         if (one_ok) {
             const int S_eff = (lens && M % S == 0) ? S : M;                 // no taps, no lens: one "sequence" of M rows
             // round 3: the LDS-DMA kernel's one-tap form (four 32 KiB buffers: three K-tiles in flight per CU instead of the
             // register-staged kernel's two) with the ATOMIC epilogue - these launches are HBM-bound and short, slabs lose here
-            static const int one_tg = fs2_dev_env("FS2_WGRAD_TG1", 1);
             // workgroups to aim for: 128 (same-box sweeps of the whole step, r03e / r03f: 64: 8.73, 96: 8.68, 128: 8.66, 160: 8.66,
             // 192: 9.53 vs 9.47 at 128 on the other box, 256: 8.73, 384+: worse; the register-staged kernel: 8.74): a workgroup holds
             // 128 KiB of LDS, i.e. a whole CU that the data-gradient chain's persistent kernels cannot use meanwhile
-            static const int one_wgs = fs2_dev_env("FS2_WGRAD_TG1_WGS", 128);
+            const int one_wgs = 128;
             bool done = false;
-            if (one_tg && !slab && (double)M * (lddy > ldx ? lddy : ldx) * 2 < 4.0e9) {
+            if ((double)M * (lddy > ldx ? lddy : ldx) * 2 < 4.0e9) {
                 WgradPlan p1 = {};
                 p1.g_first = 1; p1.n_first = 1; p1.n_rest = 0; p1.share = 1;
                 p1.tiles = fs2_cdiv(N, 128) * fs2_cdiv(Cin, 128);
@@ -1752,10 +1716,8 @@ static int conv_wgrad_impl(const void* dY, long lddy, const void* X, long ldx, f
                 // fragments - 2 LDS instructions per MFMA instead of 3; three 48 KiB ring buffers).  Same box, profiles/r06x_bench_wgrad_wide.log:
                 // decoder w_2 (Cin = 1024) 69.6 -> 55.5 us, decoder QKV (N = 768) 53.4 -> 48.3; with few tiles it LOSES (decoder fc, 2 wide
                 // tiles: 24.5 -> 29.4; every encoder shape + 2.6 - 4.3 us): only launches with >= 6 wide tiles and a long row stream take it.
-                // FS2_WGRAD_TG1_WIDE (dev builds): 0 = never, 2 = whenever Cin % 256 == 0.
-                static const int one_wide = fs2_dev_env("FS2_WGRAD_TG1_WIDE", 1);
                 const long wide_tiles = (long)fs2_cdiv(N, 128) * (Cin / 256);
-                if (Cin % 256 == 0 && (one_wide == 2 || (one_wide == 1 && M >= 16384 && wide_tiles >= 6))) { p1.share = 2; p1.tiles = (int)wide_tiles; }
+                if (Cin % 256 == 0 && M >= 16384 && wide_tiles >= 6) { p1.share = 2; p1.tiles = (int)wide_tiles; }
                 p1.units = (M / S_eff) * ((S_eff + 63) / 64);
                 long want = p1.tiles >= one_wgs ? 1 : (one_wgs + p1.tiles / 2) / p1.tiles;
                 const long max_by_units = p1.units / 8 > 0 ? p1.units / 8 : 1;
@@ -1766,10 +1728,8 @@ static int conv_wgrad_impl(const void* dY, long lddy, const void* X, long ldx, f
                 a1.S = S_eff;
                 done = fs2_wgrad_tg_launch(a1, p1, stream);
             }
-            if (!done) {
-                if (wg_waves1 == 8) launch_wgrad_bf16<1, 0, 8>(a, S_eff, 1, stream, slab ? &plan : nullptr);
-                else launch_wgrad_bf16<1, 0, 4>(a, S_eff, 1, stream, slab ? &plan : nullptr);
-            }
+            // launches the LDS-DMA kernel declines (operands of 4 GB or more): the register-staged kernel
+            if (!done) launch_wgrad_bf16<1, 0, 4>(a, S_eff, 1, stream);
             bias_fused = true;
         }
         else if (conv_ok && slab && plan.share && (double)M * (lddy > ldx ? lddy : ldx) * 2 < 4.0e9 &&
@@ -1786,15 +1746,9 @@ static int conv_wgrad_impl(const void* dY, long lddy, const void* X, long ldx, f
                 const int tps = (S + 63) / 64; const long units = (long)(M / S) * tps;
                 p3.splits = fs2_cdiv(units, p3.ups);
             }
-            if (wg_waves == 8) {
-                if (rem == 0) launch_wgrad_bf16<3, 0, 8>(a, S, g3, stream, pp);
-                else if (rem == 2) launch_wgrad_bf16<3, 2, 8>(a, S, g3, stream, pp);
-                else launch_wgrad_bf16<3, 1, 8>(a, S, g3, stream, pp);
-            } else {
-                if (rem == 0) launch_wgrad_bf16<3, 0, 4>(a, S, g3, stream, pp);
-                else if (rem == 2) launch_wgrad_bf16<3, 2, 4>(a, S, g3, stream, pp);
-                else launch_wgrad_bf16<3, 1, 4>(a, S, g3, stream, pp);
-            }
+            if (rem == 0) launch_wgrad_bf16<3, 0, 8>(a, S, g3, stream, pp);
+            else if (rem == 2) launch_wgrad_bf16<3, 2, 8>(a, S, g3, stream, pp);
+            else launch_wgrad_bf16<3, 1, 8>(a, S, g3, stream, pp);
             bias_fused = true;
         }
         else conv_wgrad_kernel<bf16_t><<<grid, 256, 0, stream>>>(a);

@@ -170,7 +170,7 @@ __device__ __forceinline__ void s_epilogue_ln(const ConvGemmArgs& a, const WLn& 
     }
 }
 
-template <int ACT, int ABL, int EPI>
+template <int ACT, int EPI>
 __device__ __forceinline__ void s_epilogue(const ConvGemmArgs& a, f32x16 (&acc)[2][1], int m0, int nbase, int fl, int fh,
                                            const float* bias_s, const int32_t* lens_s, const uint4 (&rr)[2][2]) {
     constexpr bool ANY = (EPI & S_EPI_ANY) != 0;
@@ -229,19 +229,17 @@ __device__ __forceinline__ void s_epilogue(const ConvGemmArgs& a, f32x16 (&acc)[
                 uint32_t* ou = reinterpret_cast<uint32_t*>(&o);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) ou[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-                if (ABL != 1 || o.x == 0x12345678u) *reinterpret_cast<uint4*>(yrow + n) = o;
+                *reinterpret_cast<uint4*>(yrow + n) = o;
             }
         }
     }
 }
 
 // grid stripes * (N / 256), 1-D: a workgroup walks the 64-row tiles stripe, stripe + stripes, ... of one 256-column group
-// ABL (dev builds only, never launched by the product): 1 = no stores, 2 = no epilogue, 3 = no MFMA loop, 4 = consumers only pass
-// the barriers.  SKEW: the second wave of each SIMD (waves 4..7) runs its epilogue one barrier LATE, so that on every SIMD one
-// wave's MFMAs overlap the other's epilogue VALU work (the barrier per tile otherwise keeps all waves in the same phase).  Measured
-// (r04x_s_skew.log; wave i sits on SIMD {3,0,2,1}[i % 4], so waves w and w + 4 do share one): no gain from any pairing - the kernel
-// is bound by bytes moved per CU, not by issue slots - so the product launches SKEW = 0 and the modes stay a dev switch.
-template <int ABL, int SKEW, int EPI>
+// Measured and not kept: the second wave of each SIMD (waves 4..7) running its epilogue one barrier LATE, so that on every SIMD one
+// wave's MFMAs overlap the other's epilogue VALU work (r04x_s_skew.log; wave i sits on SIMD {3,0,2,1}[i % 4], so waves w and w + 4
+// do share one): no gain from any pairing - the kernel is bound by bytes moved per CU, not by issue slots.
+template <int EPI>
 __global__ void __launch_bounds__(S_THREADS) conv_gemm_s_kernel(ConvGemmArgs a, WLn ln, int ntiles, int stripes, int groups) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -327,33 +325,11 @@ __global__ void __launch_bounds__(S_THREADS) conv_gemm_s_kernel(ConvGemmArgs a, 
     const bf16_t* Rb = reinterpret_cast<const bf16_t*>(a.R);
     const unsigned arow = (unsigned)(fl * 512);              // byte offset of the lane's row (second row block: + 32 rows)
     unsigned akey = (unsigned)(fl & 15);
-    const bool late = SKEW == 1 && wave >= 4;
     f32x16 acc[2][1];
     uint4 rr[2][2];
     int m0 = 0;
-#define S_EPILOGUE()                                                                                                            \
-    do {                                                                                                                        \
-        if (ABL == 2 || ABL == 4) {                                                                                             \
-            float sink = 0.f;                                                                                                   \
-            for (int i_ = 0; i_ < 2; ++i_)                                                                                      \
-                for (int r_ = 0; r_ < 16; ++r_) sink += acc[i_][0][r_];                                                         \
-            if (sink == 123.456f) reinterpret_cast<float*>(a.Y)[0] = sink;                                                      \
-        } else if (EPI & S_EPI_LN) {                                                                                            \
-            s_epilogue_ln(a, ln, acc, m0, nbase, wave, fl, fh, bias_s, gamma_s, beta_s, lens_s, rr, red, ln_seed, ln_ik);              \
-        } else {                                                                                                                \
-            if (EPI & S_EPI_ANY) {                                                                                              \
-                FS2_ACT_DISPATCH(a.act, (s_epilogue<ACT, ABL, EPI>(a, acc, m0, nbase, fl, fh, bias_s, lens_s, rr)));                 \
-            } else if (a.act == FS2_ACT_RELU) { /* (tanh / leaky ReLU launches take the S_EPI_ANY kernel) */                    \
-                s_epilogue<FS2_ACT_RELU, ABL, EPI>(a, acc, m0, nbase, fl, fh, bias_s, lens_s, rr);                                  \
-            } else {                                                                                                            \
-                s_epilogue<FS2_ACT_NONE, ABL, EPI>(a, acc, m0, nbase, fl, fh, bias_s, lens_s, rr);                                  \
-            }                                                                                                                   \
-        }                                                                                                                       \
-    } while (0)
     for (int t = 0; t < my_tiles; ++t) {
         s_barrier_mem();                                     // tile t has landed (all loader pieces)
-        if (ABL == 4) continue;
-        if (late && t > 0) S_EPILOGUE();                     // (tile t - 1's, from registers only)
         asm volatile("" : "+v"(akey));                       // (keeps the 16 swizzled column offsets from being hoisted into 16 registers:
                                                              //  the budget is 168 with 10 waves, and a spill is a scratch LOAD per tile)
         const unsigned char* buf = smem + (t % S_NBUF) * S_TILE_BYTES;
@@ -371,20 +347,24 @@ __global__ void __launch_bounds__(S_THREADS) conv_gemm_s_kernel(ConvGemmArgs a, 
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
-        if (ABL != 3) {
 #pragma unroll
-            for (int ks = 0; ks < 16; ++ks) {
-                const unsigned coff = ((unsigned)(2 * ks + fh) ^ akey) << 4;
-                const u32x4 a0 = *reinterpret_cast<const u32x4*>(buf + arow + coff);
-                const u32x4 a1 = *reinterpret_cast<const u32x4*>(buf + arow + 32 * 512 + coff);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[ks]), __builtin_bit_cast(bf16x8, a0), acc[0][0], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[ks]), __builtin_bit_cast(bf16x8, a1), acc[1][0], 0, 0, 0);
-            }
+        for (int ks = 0; ks < 16; ++ks) {
+            const unsigned coff = ((unsigned)(2 * ks + fh) ^ akey) << 4;
+            const u32x4 a0 = *reinterpret_cast<const u32x4*>(buf + arow + coff);
+            const u32x4 a1 = *reinterpret_cast<const u32x4*>(buf + arow + 32 * 512 + coff);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[ks]), __builtin_bit_cast(bf16x8, a0), acc[0][0], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[ks]), __builtin_bit_cast(bf16x8, a1), acc[1][0], 0, 0, 0);
         }
-        if (!late) S_EPILOGUE();
+        if (EPI & S_EPI_LN) {
+            s_epilogue_ln(a, ln, acc, m0, nbase, wave, fl, fh, bias_s, gamma_s, beta_s, lens_s, rr, red, ln_seed, ln_ik);
+        } else if (EPI & S_EPI_ANY) {
+            FS2_ACT_DISPATCH(a.act, (s_epilogue<ACT, EPI>(a, acc, m0, nbase, fl, fh, bias_s, lens_s, rr)));
+        } else if (a.act == FS2_ACT_RELU) {                  // (tanh / leaky ReLU launches take the S_EPI_ANY kernel)
+            s_epilogue<FS2_ACT_RELU, EPI>(a, acc, m0, nbase, fl, fh, bias_s, lens_s, rr);
+        } else {
+            s_epilogue<FS2_ACT_NONE, EPI>(a, acc, m0, nbase, fl, fh, bias_s, lens_s, rr);
+        }
     }
-    if (late && ABL != 4) S_EPILOGUE();
-#undef S_EPILOGUE
 }
 
 // ------------------------------------------------------------------------------------------------ launcher
@@ -408,16 +388,14 @@ bool fs2_conv_gemm_s_ok(const ConvGemmArgs& a, int dtype) {
     if (a.Cin != S_K || a.N % 256 != 0 || a.N > 256 * 64 || !a.vec_ok || a.ldx % 8 != 0) return false;
     if (a.lens && a.M / a.S > S_MAXB) return false;
     if ((double)a.M * a.ldx * 2 >= 4.0e9) return false;
-    static const int on = fs2_dev_env("FS2_GEMM_S", 1);               // dev A/B: 0 = off
-    if (!on) return false;
     return (long)fs2_cdiv(a.M, S_TM) * (a.N / 256) >= s_cu_count();
 }
 
-template <int ABL, int SKEW, int EPI>
+template <int EPI>
 static void s_launch_one(const ConvGemmArgs& a, dim3 grid, int ntiles, int stripes, int groups, hipStream_t stream, const WLn& ln = WLn{}) {
     static Fs2DevOnce once;
-    once.run([&] { (void)hipFuncSetAttribute((const void*)conv_gemm_s_kernel<ABL, SKEW, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS); });
-    conv_gemm_s_kernel<ABL, SKEW, EPI><<<grid, S_THREADS, S_LDS, stream>>>(a, ln, ntiles, stripes, groups);
+    once.run([&] { (void)hipFuncSetAttribute((const void*)conv_gemm_s_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS); });
+    conv_gemm_s_kernel<EPI><<<grid, S_THREADS, S_LDS, stream>>>(a, ln, ntiles, stripes, groups);
 }
 
 void fs2_conv_gemm_s_launch(const ConvGemmArgs& a, hipStream_t stream) {
@@ -428,28 +406,19 @@ void fs2_conv_gemm_s_launch(const ConvGemmArgs& a, hipStream_t stream) {
     if (stripes > ntiles) stripes = groups > 1 ? ntiles / 8 * 8 : ntiles;
     if (stripes < 8) { stripes = 8; }                        // (tiles past ntiles: a stripe with no tile returns at once)
     const dim3 grid((unsigned)(stripes * groups));
-#ifdef FS2_DEV
-    static const int abl = fs2_dev_env("FS2_S_ABL", 0), skew = fs2_dev_env("FS2_S_SKEW", 0), any = fs2_dev_env("FS2_S_EPI_ANY", 0);
-    if (skew == 1) { s_launch_one<0, 1, S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); return; }
-    if (abl == 1) { s_launch_one<1, 0, S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); return; }
-    if (abl == 2) { s_launch_one<2, 0, S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); return; }
-    if (abl == 3) { s_launch_one<3, 0, S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); return; }
-    if (abl == 4) { s_launch_one<4, 0, S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); return; }
-    if (any) { s_launch_one<0, 0, S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); return; }
-#endif
     // the epilogue this launch needs (see s_epilogue): accumulate / a scale fall back to the run-time-flag form
     const bool gate = a.act == FS2_ACT_GATE;
     const bool odd_act = a.act == FS2_ACT_TANH || a.act == FS2_ACT_LRELU;
     int epi = (a.accumulate || a.out_scale != 1.0f || (gate && !a.R) || odd_act) ? S_EPI_ANY
               : ((a.R ? (gate ? S_EPI_GATE : S_EPI_RES) : 0) | (a.lens ? S_EPI_LENS : 0));
     switch (epi) {
-        case 0: s_launch_one<0, 0, 0>(a, grid, ntiles, stripes, groups, stream); break;
-        case S_EPI_RES: s_launch_one<0, 0, S_EPI_RES>(a, grid, ntiles, stripes, groups, stream); break;
-        case S_EPI_GATE: s_launch_one<0, 0, S_EPI_GATE>(a, grid, ntiles, stripes, groups, stream); break;
-        case S_EPI_LENS: s_launch_one<0, 0, S_EPI_LENS>(a, grid, ntiles, stripes, groups, stream); break;
-        case S_EPI_RES | S_EPI_LENS: s_launch_one<0, 0, S_EPI_RES | S_EPI_LENS>(a, grid, ntiles, stripes, groups, stream); break;
-        case S_EPI_GATE | S_EPI_LENS: s_launch_one<0, 0, S_EPI_GATE | S_EPI_LENS>(a, grid, ntiles, stripes, groups, stream); break;
-        default: s_launch_one<0, 0, S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); break;
+        case 0: s_launch_one<0>(a, grid, ntiles, stripes, groups, stream); break;
+        case S_EPI_RES: s_launch_one<S_EPI_RES>(a, grid, ntiles, stripes, groups, stream); break;
+        case S_EPI_GATE: s_launch_one<S_EPI_GATE>(a, grid, ntiles, stripes, groups, stream); break;
+        case S_EPI_LENS: s_launch_one<S_EPI_LENS>(a, grid, ntiles, stripes, groups, stream); break;
+        case S_EPI_RES | S_EPI_LENS: s_launch_one<S_EPI_RES | S_EPI_LENS>(a, grid, ntiles, stripes, groups, stream); break;
+        case S_EPI_GATE | S_EPI_LENS: s_launch_one<S_EPI_GATE | S_EPI_LENS>(a, grid, ntiles, stripes, groups, stream); break;
+        default: s_launch_one<S_EPI_ANY>(a, grid, ntiles, stripes, groups, stream); break;
     }
 }
 
@@ -462,5 +431,5 @@ void fs2_conv_gemm_s_ln_launch(const ConvGemmArgs& a, const WLn& ln, hipStream_t
     const int ntiles = fs2_cdiv(a.M, S_TM);
     int stripes = s_cu_count();
     if (stripes > ntiles) stripes = ntiles;
-    s_launch_one<0, 0, S_EPI_LN>(a, dim3((unsigned)stripes), ntiles, stripes, 1, stream, ln);
+    s_launch_one<S_EPI_LN>(a, dim3((unsigned)stripes), ntiles, stripes, 1, stream, ln);
 }

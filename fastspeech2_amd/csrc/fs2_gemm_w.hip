@@ -400,7 +400,7 @@ extern "C" int fs2_gemm_res_ln_fwd(const void* X, long ldx, const void* Wpacked,
     ConvGemmArgs a = {};
     a.X = X; a.ldx = ldx; a.W = Wpacked; a.ldw = Cin; a.bias = bias; a.R = R; a.ldr = ldr; a.Y = Z; a.ldy = ldz; a.lens = lens;
     a.M = M; a.N = N; a.Cin = Cin; a.S = S; a.taps = 1; a.dil = 1; a.pad = 0; a.act = FS2_ACT_NONE; a.slope = 0.f; a.in_act = FS2_ACT_NONE;
-    a.in_slope = 0.f; a.accumulate = 0; a.out_scale = 1.f; a.vec_ok = 1; a.dbg = 0;
+    a.in_slope = 0.f; a.accumulate = 0; a.out_scale = 1.f; a.vec_ok = 1;
     WLn ln;
     ln.gamma = gamma; ln.beta = beta; ln.out = out; ln.ldo = ldo; ln.mean = mean; ln.rstd = rstd; ln.eps = eps; ln.p_pre = p_pre;
     ln.seed_pre = seed_pre; ln.seed_dev = seed_dev;

@@ -210,8 +210,7 @@ extern "C" int fs2_ln_fwd(void* y, const void* res, const float* gamma, const fl
     a.rows = B * S; a.S = S; a.C = C; a.eps = eps; a.p_pre = p_pre; a.p_post = p_post; a.seed_pre = seed_pre; a.seed_post = seed_post;
     a.seed_dev = seed_dev;
     if (a.rows == 0) return FS2_OK;
-    static const int ln_fast = fs2_dev_env("FS2_LN_FAST", 3);       // dev A/B only: bit 0 forward, bit 1 backward
-    if ((ln_fast & 1) && dtype == FS2_BF16 && C == 256 && (((uintptr_t)y | (uintptr_t)res | (uintptr_t)out) & 15) == 0) {
+    if (dtype == FS2_BF16 && C == 256 && (((uintptr_t)y | (uintptr_t)res | (uintptr_t)out) & 15) == 0) {
         ln_fwd_c256_bf16_kernel<2><<<fs2_cdiv(a.rows, 16), 256, 0, stream>>>(a);
         FS2_CHECK_LAUNCH("ln_fwd");
         return FS2_OK;
@@ -535,8 +534,7 @@ extern "C" int fs2_ln_bwd_sum(const void* z, const void* dout, const void* dout2
     int grid = fs2_cdiv(a.rows, 8);
     if (grid > FS2_LN_BWD_GRID) grid = FS2_LN_BWD_GRID;
     const bool al16 = ((((uintptr_t)z | (uintptr_t)dout | (uintptr_t)dout2 | (uintptr_t)d1_add | (uintptr_t)d1 | (uintptr_t)d2) & 15) == 0);
-    static const int ln_fast = fs2_dev_env("FS2_LN_FAST", 3);
-    if ((ln_fast & 2) && dtype == FS2_BF16 && C == 256 && al16) {
+    if (dtype == FS2_BF16 && C == 256 && al16) {
         const int iters = fs2_cdiv(a.rows, 16 * FS2_LN_BWD_GRID);        // same trip count for every wave
         grid = fs2_cdiv(a.rows, 16 * iters);
         ln_bwd_c256_bf16_kernel<<<grid, 512, 0, stream>>>(a);
@@ -759,8 +757,6 @@ __global__ void bn_stats_fix_kernel(const T* __restrict__ x, float* __restrict__
 // workgroup spills (r02m: statistics 19.9 -> 29.7 us, backward sums 53.8 -> 82.7 us; apply 28.9 -> 27.8, dx 34.4 -> 33.5).
 static int bn_vec(const BnArgs& a, int C, int dtype) {
     const uintptr_t al = (uintptr_t)a.x | (uintptr_t)a.dout | (uintptr_t)a.res | (uintptr_t)a.out;
-    static const int vec_env = fs2_dev_env("FS2_BN_VEC", 8);       // dev A/B only
-    if (vec_env == 4) return 4;
     return (dtype == FS2_BF16 && C % 8 == 0 && (al & 15) == 0) ? 8 : 4;
 }
 // cblk = 0: a workgroup spans whole rows (the streaming modes).  cblk > 0: a workgroup owns cblk channels and grid.y walks
@@ -769,8 +765,6 @@ static int bn_vec(const BnArgs& a, int C, int dtype) {
 // half of the backward-sums pass (r02m: 54 us against 34 us for the dx pass that does the same arithmetic AND stores).  64-
 // channel blocks leave 32 row groups: 8x fewer atomics at the same number of workgroups, 128-byte row segments per wave.
 static dim3 bn_geometry(BnArgs& a, int M, int C, int nthreads, int want_blocks, int vec, int cblk = 0) {
-    static const int cblk_env = fs2_dev_env("FS2_BN_CBLK", 1);       // dev A/B: 0 = whole-row workgroups in the reducing modes too
-    if (!cblk_env) cblk = 0;
     int cpr = (cblk > 0 && cblk < C ? cblk : C) / vec, cprp = 1;
     while (cprp < cpr) cprp <<= 1;
     a.cprp = cprp;

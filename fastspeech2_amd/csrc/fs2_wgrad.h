@@ -9,7 +9,7 @@ struct WgradArgs {
     float* dW;
     float* dbias;          // optional: dbias[n] += sum_m dY[m][n], fused into the blocks that own (c-tile 0, tap group 0)
     const int32_t* lens;   // optional: dY rows t >= lens[seq] are known to be zero -> their K-tiles are skipped
-    int M, N, Cin, S, taps, dil, pad, rows_per_split, g3, dbg;
+    int M, N, Cin, S, taps, dil, pad, rows_per_split, g3;
     int n_tiles, n_splits, per_xcd;   // fs2_wgrad.hip's 1-D grid (XCD-aware placement of (split, tile) pairs; see conv_wgrad_tg_kernel)
     float* slab;           // optional split-K scratch: split s stores its partial tile (plain stores) at slab + s * slab_stride in the
     long slab_stride;      // layout of dW, its bias partials behind it (slab_stride = N*taps*Cin + N floats); wgrad_finalize_kernel
@@ -40,7 +40,7 @@ static inline WgradPlan wgrad_plan(int M, int N, int Cin, int S, int taps, int d
         // workgroups to aim for: 192, not one per CU - these launches run on the side stream NEXT TO the data-gradient chain, whose
         // persistent kernels need whole CUs (r03d same-box sweep of the whole step, two rounds: 64: 10.56 ms, 96: 9.55, 128: 9.31,
         // 160: 9.23, 192: 9.22, 256: 9.27, 384 .. 1024: 9.41 - 9.45; the round-2 atomic kernels: 9.44; no weight gradients: 7.88)
-        static const int cus = fs2_dev_env("FS2_WGRAD_TG_WGS", 192);
+        const int cus = 192;
         long want = p.tiles >= cus ? 1 : (cus + p.tiles / 2) / p.tiles;       // round(cus / tiles)
         const long max_by_units = p.units / 8 > 0 ? p.units / 8 : 1;
         if (want > max_by_units) want = max_by_units;

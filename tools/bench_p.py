@@ -1,13 +1,10 @@
 """Dev tool: the train step's large contractions at production shapes (B=48, T=925 / L=128, the bench batch's own ragged
-lengths) - persistent kernel vs ring / 128^2 kernels, with the dev library's ablation switches.
+lengths), timed with HIP events on the kernels the library dispatches them to.
 
-    python tools/bench_p.py                 one process, current environment
-    python tools/bench_p.py sweep           re-runs itself under FS2_LIB_PATH=libfs2hip_dev.so with FS2_GEMM_P / FS2_GEMM_ABL /
-                                            FS2_GEMM_DBG settings and prints one table (A/B on the same box)
+    python tools/bench_p.py                 one process, current environment (FS2_LIB_PATH selects another build)
 """
 import math
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,7 +25,7 @@ def run():
     lens_by_S = {b["max_mel_len"]: b["mel_lens"].to(torch.int32).to(dev), 128: b["src_lens"].to(torch.int32).to(dev)}
     T = b["max_mel_len"]
     out = []
-    tws = ops.tail_workspace(dev)                                  # as the engine passes it (dev library: FS2_P_TKS=1 turns the split off)
+    tws = ops.tail_workspace(dev)                                  # as the engine passes it
     for (name, Cin, Cout, k, S) in SHAPES:
         S = T if S == 925 else S
         M = 48 * S
@@ -55,32 +52,5 @@ def run():
     print("RESULT " + ";".join(f"{n}|{us:.1f}|{tf:.0f}" for n, us, tf in out), flush=True)
 
 
-def sweep(custom=None):
-    cfgs = [(c, dict(kv.split("=") for kv in c.split(",") if kv)) for c in custom] if custom else [("ring/128 (P off)", {"FS2_GEMM_P": "0"}), ("persistent", {}), ("P no-MFMA", {"FS2_GEMM_ABL": "1"}),
-            ("P no-reads", {"FS2_GEMM_ABL": "2"}), ("P no-MFMA no-reads", {"FS2_GEMM_ABL": "3"}), ("P no-epilogue", {"FS2_GEMM_ABL": "4"}),
-            ]
-    rows = {}
-    for tag, env in cfgs:
-        e = dict(os.environ)
-        e["FS2_LIB_PATH"] = os.path.join(ROOT, "fastspeech2_amd", "libfs2hip_dev.so")
-        e.update(env)
-        p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=e, capture_output=True, text=True, timeout=600)
-        line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-        if not line:
-            print(f"{tag}: FAILED\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
-            continue
-        rows[tag] = [x.split("|") for x in line[0][7:].split(";")]
-    names = [r[0] for r in next(iter(rows.values()))]
-    print("| shape | " + " | ".join(rows) + " |")
-    print("|---|" + "---|" * len(rows))
-    for i, n in enumerate(names):
-        print(f"| {n} | " + " | ".join(f"{rows[t][i][1]} us / {rows[t][i][2]} TF" for t in rows) + " |")
-
-
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "sweep":
-        sweep()
-    elif len(sys.argv) > 1 and sys.argv[1] == "ab":          # python tools/bench_p.py ab FS2_P_ORDER=0 FS2_P_ORDER=1,FS2_X=2 ...
-        sweep(sys.argv[2:])
-    else:
-        run()
+    run()

@@ -1,5 +1,5 @@
-"""Dev tool: the one-tap contractions of a decoder FFT block (B=48, T=925) forward and data gradient, timed with HIP events;
-run it under FS2_LIB_PATH=...dev.so with FS2_GEMM_W=0 / 1 to compare the wide-tile kernel with the persistent 256x128 one."""
+"""Dev tool: the one-tap contractions of a decoder FFT block (B=48, T=925) forward and data gradient, timed with HIP events on
+the kernels the library dispatches them to (the wide-tile kernel where N % 256 == 0); FS2_LIB_PATH selects another build to compare."""
 import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
