@@ -316,7 +316,8 @@ typedef FragAddrT<16384, 256> FragAddr;                  // 64-row tile images, 
 // of the 64 two-byte stores of the column-per-lane form - a store-issue-bound tail of the order of a tenth of a workgroup's life),
 // and every per-row factor (the online-softmax rescale, 1 / l, the softmax scale) is a per-LANE scalar: no cross-lane shuffles.
 typedef unsigned attn_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void attn_store_row(bf16_t* rowp, const f32x16 (&acc)[4], float f, int h2, bool ok) {
+// live = false stores zeros by a SELECT, not by f = 0: an accumulator that overflowed (a padded key's row in dK / dV) times 0 is NaN.
+__device__ __forceinline__ void attn_store_row(bf16_t* rowp, const f32x16 (&acc)[4], float f, int h2, bool ok, bool live = true) {
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
         float c[2][8];
@@ -327,11 +328,12 @@ __device__ __forceinline__ void attn_store_row(bf16_t* rowp, const f32x16 (&acc)
             c[0][e] = __uint_as_float(s0[0]); c[0][4 + e] = __uint_as_float(s0[1]);
             c[1][e] = __uint_as_float(s1[0]); c[1][4 + e] = __uint_as_float(s1[1]);
         }
+        auto y = [&](float x) { return live ? x * f : 0.f; };
 #pragma unroll
         for (int ch = 0; ch < 2; ++ch) {
             uint4 o;
-            o.x = pack_bf16x2(c[ch][0] * f, c[ch][1] * f); o.y = pack_bf16x2(c[ch][2] * f, c[ch][3] * f);
-            o.z = pack_bf16x2(c[ch][4] * f, c[ch][5] * f); o.w = pack_bf16x2(c[ch][6] * f, c[ch][7] * f);
+            o.x = pack_bf16x2(y(c[ch][0]), y(c[ch][1])); o.y = pack_bf16x2(y(c[ch][2]), y(c[ch][3]));
+            o.z = pack_bf16x2(y(c[ch][4]), y(c[ch][5])); o.w = pack_bf16x2(y(c[ch][6]), y(c[ch][7]));
             if (ok) *reinterpret_cast<uint4*>(rowp + nb * 32 + ch * 16 + h2 * 8) = o;
         }
     }
@@ -789,11 +791,10 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dkv2_bf16_kernel(const bf16_t
         FS2_STAMP(10);
     }
     // (transposed accumulators dK^T / dV^T [d][key]: lane = key)
-    {
-        const float kz = mykey < len ? 1.f : 0.f;           // a padded key's rows come out as zeros
-        attn_store_row(dK + (size_t)min(mykey, S - 1) * ld, dk, scale * kz, h2, mykey < S);
-        attn_store_row(dV + (size_t)min(mykey, S - 1) * ld, dv, kz, h2, mykey < S);
-    }
+    // a padded key's rows come out as zeros, selected: its probabilities were never masked, and when its score exceeds a query's
+    // lse by more than 128 log2 units they overflow, so its accumulators may hold inf / NaN
+    attn_store_row(dK + (size_t)min(mykey, S - 1) * ld, dk, scale, h2, mykey < S, mykey < len);
+    attn_store_row(dV + (size_t)min(mykey, S - 1) * ld, dv, 1.f, h2, mykey < S, mykey < len);
 }
 #undef FS2_STAMP_KERNEL
 // (also computes delta[q] = sum_d dO[q][d] O[q][d] for its queries - a lane already holds half of its query's dO row - and
