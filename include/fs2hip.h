@@ -296,6 +296,30 @@ int fs2_stft_mel_epilogue(const float* ft, long ldft, const float* mel_basis, co
                           float* energy, int B, int S, int frames, int NF, int n_mel, float clamp_min,
                           fs2_stream_t stream);
 
+/* ---- Griffin-Lim mel inversion (audio/stft.py:52-122, audio/audio_processing.py:7-82, audio/tools.py:18-34) ----
+ * Frame-major rows: utterance b owns rows [b*Fmax, (b+1)*Fmax) of which frames[b] are frames (frames == NULL: all Fmax);
+ * G rows are [m cos(phi) (NF) | m sin(phi) (NF) | 0 up to ldg], the inverse GEMM's input.  Every padding entry (rows
+ * f >= frames[b], columns >= 2 NF) is written as 0.  Strided operands: element (b, f, k) at b*sb + f*sf + k*sk.
+ * fs2_gl_mel_to_mag: log-mel (element (b, j, t) at b*sb + j*sj + t*st) -> mag[b][f][k] (row stride ldm) =
+ * 1000 * exp(mel[b][:, f]) . mel_basis[:, k] over the filters' bands, f < mel_lens[b] - 1 (the last frame dropped), 0 beyond. */
+int fs2_gl_mel_to_mag(const float* mel, long sb, long sj, long st, const int32_t* mel_lens, const float* mel_basis,
+                      const int32_t* span, float* mag, long ldm, int B, int Fmax, int n_mel, int NF, fs2_stream_t stream);
+/* stft.py:84-86: G = [mag cos(phase) ; mag sin(phase)] */
+int fs2_gl_recombine(const float* mag, long msb, long msf, long msk, const float* phase, long psb, long psf, long psk,
+                     const int32_t* frames, float* G, long ldg, int B, int Fmax, int NF, fs2_stream_t stream);
+/* audio_processing.py:77-79: forward-DFT rows ft[b*S + f] (Re | Im) -> G = [mag cos(atan2(Im, Re)) ; mag sin(atan2(Im, Re))] */
+int fs2_gl_project(const float* ft, long ldft, int S, const float* mag, long msb, long msf, long msk, const int32_t* frames,
+                   float* G, long ldg, int B, int Fmax, int NF, fs2_stream_t stream);
+/* stft.py:88-120: overlap-add of the inverse GEMM's per-frame segments seg[b*Fmax + f][0, filter) in increasing f, divided by
+ * window_sumsquare (win_sq: the squared, centre-padded window, filter_length doubles) where it exceeds tiny(float32), times
+ * filter/hop, trimmed by filter/2 at both ends: N_b = hop (frames[b] - 1) samples.  xp (optional): the reflect-padded rows the
+ * next forward DFT reads (row_len >= hop (Fmax - 1) + filter; reflected at each utterance's own end, zero beyond);
+ * y (optional): the signal rows (ldy >= hop (Fmax - 1); zero beyond N_b). */
+int fs2_gl_ola(const float* seg, long lds, const int32_t* frames, const double* win_sq, float* xp, long row_len, float* y,
+               long ldy, int B, int Fmax, int filter_length, int hop_length, fs2_stream_t stream);
+/* stft.py:74-81: ft rows -> magnitude, phase = atan2(Im, Re), each (B, NF, F) */
+int fs2_gl_mag_phase(const float* ft, long ldft, int S, float* mag, float* phase, int B, int F, int NF, fs2_stream_t stream);
+
 /* ---- loss (model/loss.py:19-92): masked L1 (mel, post-net mel) + masked MSE (pitch, energy, log-duration) ----
  * mel / post: [B][T][n_mel] f32 predictions; mel_t: target with batch stride ld_t_b (its own padded length >= T);
  * lens int64 (valid = t < min(len, T)); p/e predictions [B][L] (phoneme level) or [B][T] (p_frame / e_frame = 1) with

@@ -5,6 +5,7 @@
     python synthesize.py --restore_step N --mode single --text "{HH AH0 L OW1}" -p ... -m ... -t ...
 
 The acoustic model and the HiFi-GAN generator run as HIP kernels; wavs land in train_config.path.result_path.
+With --griffin_iters N the wavs come from N Griffin-Lim iterations on the post-net mel instead (no vocoder checkpoint needed).
 Batch mode reads phoneme strings (the `{...}` field of train.txt / val.txt), exactly what the reference's TextDataset
 does.  Single mode takes the phoneme string directly: the grapheme-to-phoneme step of the reference (g2p_en / pypinyin +
 lexicon, synthesize.py:20-84) is host-side string processing outside the hot path and its packages are not in this
@@ -34,6 +35,27 @@ def synthesize(model, step, configs, vocoder, batchs, control_values, device=Non
     pipeline = SynthPipeline(model, vocoder, configs, control_values, device=device, path=train_config["path"]["result_path"],
                              write=True)
     for batch, _output, _wavs in pipeline(DevicePrefetcher(batchs, device)):
+        n += len(batch[0])
+    return n
+
+
+def synthesize_griffin_lim(model, configs, batchs, control_values, n_iters, device=None):
+    """--griffin_iters N: the post-net mel of each utterance (cut at its mel_len) -> Griffin-Lim (N iterations, audio/tools.py:18-34
+    inv_mel_spec on the GPU, one ragged launch sequence per batch) -> float32 wavs; no vocoder is loaded."""
+    from fastspeech2_amd.audio import TacotronSTFT, mels_to_wavs_griffin_lim
+    from fastspeech2_amd.utils import _write_wavs
+    preprocess_config, model_config, train_config = configs
+    pitch_control, energy_control, duration_control = control_values
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    st, mel = preprocess_config["preprocessing"]["stft"], preprocess_config["preprocessing"]["mel"]
+    stft = TacotronSTFT(st["filter_length"], st["hop_length"], st["win_length"], mel["n_mel_channels"],
+                        preprocess_config["preprocessing"]["audio"]["sampling_rate"], mel["mel_fmin"], mel["mel_fmax"]).to(device)
+    n = 0
+    for batch in DevicePrefetcher(batchs, device):
+        with torch.no_grad():
+            out = model(*(batch[2:]), p_control=pitch_control, e_control=energy_control, d_control=duration_control)
+            wavs = mels_to_wavs_griffin_lim(out[1].transpose(1, 2), out[9], stft, n_iters)
+        _write_wavs(train_config["path"]["result_path"], batch[0], wavs, preprocess_config)
         n += len(batch[0])
     return n
 
@@ -71,6 +93,8 @@ def parse_args(argv=None):
                         help="HIP hardware queues of this process (GPU_MAX_HW_QUEUES; the runtime default 4 makes streams share queues: "
                              "utils.SynthPipeline / the engine's side streams); the same for every world size; an exported value wins; 0 = leave the runtime default")
     parser.add_argument("--random_vocoder", action="store_true", help="allow a random-init vocoder when no checkpoint exists (smoke runs)")
+    parser.add_argument("--griffin_iters", type=int, default=0,
+                        help="N > 0: waveforms by N Griffin-Lim iterations on the post-net mel (float32 wavs, no vocoder loaded); 0 = HiFi-GAN")
     return parser.parse_args(argv)
 
 
@@ -86,8 +110,8 @@ def main(args):
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     device = torch.device("cuda", torch.cuda.current_device())
     model = get_model(args, configs, device, train=False, compute_dtype=args.dtype)
-    vocoder = get_vocoder(model_config, device, hifigan_dir=args.hifigan_dir, compute_dtype=args.vocoder_dtype,
-                          allow_random_init=args.random_vocoder)
+    vocoder = None if args.griffin_iters > 0 else get_vocoder(model_config, device, hifigan_dir=args.hifigan_dir,
+                                                              compute_dtype=args.vocoder_dtype, allow_random_init=args.random_vocoder)
     if args.mode == "batch":
         dataset = TextDataset(args.source, preprocess_config)
         mine = list(range(rank, len(dataset), world))          # replicas only: each GPU takes every world-th utterance
@@ -95,8 +119,11 @@ def main(args):
                   for s in range(0, len(mine), args.batch_size))
     else:
         batchs = single_batch(args, preprocess_config)
-    n = synthesize(model, args.restore_step, configs, vocoder, batchs,
-                   (args.pitch_control, args.energy_control, args.duration_control), device=device)
+    controls = (args.pitch_control, args.energy_control, args.duration_control)
+    if args.griffin_iters > 0:
+        n = synthesize_griffin_lim(model, configs, batchs, controls, args.griffin_iters, device=device)
+    else:
+        n = synthesize(model, args.restore_step, configs, vocoder, batchs, controls, device=device)
     print(f"[rank {rank}] synthesized {n} utterances -> {train_config['path']['result_path']}")
 
 

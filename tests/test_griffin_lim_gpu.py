@@ -1,0 +1,183 @@
+"""Griffin-Lim mel inversion on the GPU (fastspeech2_amd.audio STFT / griffin_lim / inv_mel_spec / mels_to_wavs_griffin_lim,
+csrc/fs2_griffin_lim.hip + the fp32 framed-DFT GEMMs) against the live reference's fp32 results (tests/golden/griffin_lim.npz,
+per-quantity bars = 4 x the reference's own distance from an fp64 evaluation), the ragged batch against its utterances
+alone, and synthesize.py --griffin_iters."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import gl_ref
+from tests.helpers import load_golden
+
+pytestmark = pytest.mark.gpu
+G64 = gl_ref.STFT(1024, 256, 1024)
+
+
+@pytest.fixture(scope="module")
+def g():
+    return load_golden("griffin_lim")
+
+
+@pytest.fixture(scope="module")
+def stft(dev):
+    from fastspeech2_amd.audio import TacotronSTFT
+    return TacotronSTFT(1024, 256, 1024, 80, 22050, 0, 8000).to(dev)
+
+
+def _angles(g, i):
+    np.random.seed(int(g[f"u{i}_seed"]))
+    return np.angle(np.exp(2j * np.pi * np.random.rand(1, 513, g[f"u{i}_spec"].shape[-1]))).astype(np.float32)
+
+
+def _err(got, ref):
+    return float(np.abs(np.asarray(got, np.float64) - ref).max())
+
+
+def test_transform_matches_reference(dev, g, stft):
+    for i in (0, 1):
+        mag, phase = stft.stft_fn.transform(torch.from_numpy(g[f"u{i}_sig0"]).to(dev))
+        mag, phase = mag.cpu().numpy(), phase.cpu().numpy()
+        ref_mag, ref_phase = g[f"u{i}_mag"], g[f"u{i}_phase"]
+        assert mag.shape == ref_mag.shape == (1, 513, g[f"u{i}_spec"].shape[-1])
+        assert _err(mag, ref_mag) <= g[f"bar_mag_{i}"], (i, _err(mag, ref_mag), float(g[f"bar_mag_{i}"]))
+        keep = ref_mag > 1e-3 * ref_mag.max()
+        d = gl_ref.phase_distance(phase, ref_phase)[keep].max()
+        assert d <= g[f"bar_phase_{i}"], (i, d, float(g[f"bar_phase_{i}"]))
+
+
+def test_inverse_matches_reference_at_every_length(dev, g, stft):
+    for i in range(3):
+        spec = torch.from_numpy(g[f"u{i}_spec"]).to(dev)
+        y = stft.stft_fn.inverse(spec, torch.from_numpy(_angles(g, i)).to(dev)).cpu().numpy()
+        ref = g[f"u{i}_sig0"]
+        assert y.shape == (1, 1, ref.shape[1])
+        e = _err(y[:, 0], ref)
+        assert e <= g[f"bar_sig0_{i}"], (i, e, float(g[f"bar_sig0_{i}"]))
+        # the envelope edges (first / last filter_length samples, where fewer frames overlap) are inside that max; say so
+        assert _err(y[0, 0, :1024], ref[0, :1024]) <= g[f"bar_sig0_{i}"] and _err(y[0, 0, -1024:], ref[0, -1024:]) <= g[f"bar_sig0_{i}"]
+
+
+def test_griffin_lim_iterations_match_reference(dev, g, stft):
+    from fastspeech2_amd.audio import griffin_lim
+    for i in (0, 1):
+        spec = torch.from_numpy(g[f"u{i}_spec"]).to(dev)
+        for n in (0, 1, 2):
+            y = griffin_lim(spec, stft.stft_fn, n, angles=g[f"u{i}_angles"]).cpu().numpy()
+            e = _err(y, g[f"u{i}_sig{n}"])
+            assert e <= g[f"bar_sig{n}_{i}"], (i, n, e, float(g[f"bar_sig{n}_{i}"]))
+        # angles=None draws from numpy's global generator exactly as the reference does
+        np.random.seed(int(g[f"u{i}_seed"]))
+        y_drawn = griffin_lim(spec, stft.stft_fn, 2).cpu().numpy()
+        assert np.array_equal(y_drawn, griffin_lim(spec, stft.stft_fn, 2, angles=g[f"u{i}_angles"]).cpu().numpy())
+
+
+def test_griffin_lim_60_iterations_spectral_convergence(dev, g, stft):
+    from fastspeech2_amd.audio import griffin_lim
+    for i in range(3):
+        spec = g[f"u{i}_spec"]
+        y = griffin_lim(torch.from_numpy(spec).to(dev), stft.stft_fn, 60, angles=_angles(g, i)).cpu().numpy()
+        sc = gl_ref.spectral_convergence(y, spec, G64)
+        ref = float(g[f"u{i}_sc60"])
+        assert abs(sc - ref) <= 0.02 * ref, (i, sc, ref)
+
+
+def test_mel_to_magnitude_matches_reference(dev, g, stft):
+    from fastspeech2_amd import _lib, ops
+    for i in range(3):
+        mel = torch.from_numpy(g[f"u{i}_mel"]).to(dev)[None]
+        T = mel.shape[-1]
+        mag = torch.full((1, T - 1, 513), float("nan"), device=dev)
+        lens = torch.tensor([T], dtype=torch.int32, device=dev)
+        _lib.call("fs2_gl_mel_to_mag", mel.data_ptr(), mel.stride(0), mel.stride(1), mel.stride(2), lens.data_ptr(),
+                  stft.mel_basis.data_ptr(), stft.mel_span.data_ptr(), mag.data_ptr(), mag.stride(1), 1, T - 1, 80, 513, ops._stream())
+        e = _err(mag.transpose(1, 2).cpu().numpy(), g[f"u{i}_spec"])
+        assert e <= g[f"bar_spec_{i}"], (i, e, float(g[f"bar_spec_{i}"]))
+
+
+def _ragged_mels(g):
+    """five utterances of distinct lengths: the fixture's three and two cut from the longest; junk beyond each length"""
+    lens = [5, 18, 101, 40, 63]
+    srcs = [g["u0_mel"], g["u1_mel"], g["u2_mel"], g["u2_mel"][:, 7:47], g["u2_mel"][:, 30:93]]
+    mels = np.full((5, 80, 110), 50.0, dtype=np.float32)            # exp(50) * 1000 would overflow fp32 if read
+    for b, m in enumerate(srcs):
+        mels[b, :, :lens[b]] = m
+    return mels, lens
+
+
+def test_ragged_batch_equals_each_utterance_alone(dev, g, stft):
+    from fastspeech2_amd.audio import mels_to_wavs_griffin_lim
+    mels, lens = _ragged_mels(g)
+    np.random.seed(5)
+    batch = mels_to_wavs_griffin_lim(torch.from_numpy(mels).to(dev), lens, stft, n_iters=3)
+    np.random.seed(5)
+    for b, n in enumerate(lens):
+        alone = mels_to_wavs_griffin_lim(torch.from_numpy(mels[b:b + 1, :, :n].copy()).to(dev), [n], stft, n_iters=3)[0]
+        assert batch[b].dtype == np.float32 and batch[b].shape == (256 * (n - 2),)
+        assert np.isfinite(batch[b]).all() and np.array_equal(batch[b], alone), b
+
+
+def test_padding_poison_does_not_reach_outputs(dev, g, stft):
+    from fastspeech2_amd.audio import mels_to_wavs_griffin_lim
+    mels, lens = _ragged_mels(g)
+    m = torch.from_numpy(mels).to(dev)
+    np.random.seed(6)
+    clean = mels_to_wavs_griffin_lim(m, lens, stft, n_iters=2)
+    ws = stft.stft_fn.workspace(len(lens), max(lens) - 1, dev)
+    for t in ws.values():
+        t.fill_(float("nan"))
+    np.random.seed(6)
+    poisoned = mels_to_wavs_griffin_lim(m, lens, stft, n_iters=2, ws=ws)
+    for a, b in zip(clean, poisoned):
+        assert np.isfinite(b).all() and np.array_equal(a, b)
+
+
+def test_inv_mel_spec_writes_the_reference_wav(dev, g, stft, tmp_path):
+    from scipy.io import wavfile
+    from fastspeech2_amd.audio import inv_mel_spec
+    np.random.seed(int(g["u1_seed"]))
+    path = str(tmp_path / "inv.wav")
+    inv_mel_spec(torch.from_numpy(g["u1_mel"]), path, stft, griffin_iters=2)
+    sr, wav = wavfile.read(path)
+    ref = g["inv_wav"]
+    assert sr == 22050 and wav.dtype == np.float32 and wav.shape == ref.shape
+    # the target magnitude is this build's exp(mel) . mel_basis (within bar_spec of the reference's), hence 2 x the bar
+    assert _err(wav, ref) <= 2 * g["bar_sig2_1"], (_err(wav, ref), float(g["bar_sig2_1"]))
+
+
+def test_synthesize_cli_griffin_lim_without_vocoder_files(dev, tmp_path):
+    import yaml
+    from scipy.io import wavfile
+    import synthesize as synth_cli
+    import train as train_cli
+    from fastspeech2_amd.data import DevicePrefetcher, TextDataset
+    from fastspeech2_amd.utils import get_model
+    from tests.test_cli_gpu import _write_configs
+    (pp, mp, tp), tcfg = _write_configs(str(tmp_path))
+    cfgs = tuple(yaml.load(open(p), Loader=yaml.FullLoader) for p in (pp, mp, tp))
+    torch.manual_seed(0)
+    train_cli.main(train_cli.parse_args(["-p", pp, "-m", mp, "-t", tp, "--no_vocoder"]), cfgs)
+    # a step-7 checkpoint = step 6 with the log-duration predictor's bias raised by 1.5: every utterance gets enough frames
+    ck = torch.load(os.path.join(tcfg["path"]["ckpt_path"], "6.pth.tar"), map_location="cpu")
+    ck["model"]["variance_adaptor.duration_predictor.linear_layer.bias"] += 1.5
+    torch.save(ck, os.path.join(tcfg["path"]["ckpt_path"], "7.pth.tar"))
+    src = os.path.join(cfgs[0]["path"]["preprocessed_path"], "val.txt")
+    argv = ["--restore_step", "7", "--mode", "batch", "--source", src, "-p", pp, "-m", mp, "-t", tp, "--batch_size", "4",
+            "--griffin_iters", "4", "--hifigan_dir", str(tmp_path / "no_hifigan_here")]
+    sargs = synth_cli.parse_args(argv)
+    synth_cli.main(sargs)
+    # the mel lengths the acoustic model gives these utterances
+    model = get_model(sargs, cfgs, dev, train=False)
+    ds = TextDataset(src, cfgs[0])
+    names, lens = [], []
+    batchs = (ds.collate_fn([ds[i] for i in range(s, min(s + 4, len(ds)))]) for s in range(0, len(ds), 4))
+    with torch.no_grad():
+        for batch in DevicePrefetcher(batchs, dev):
+            out = model(*(batch[2:]))
+            names += list(batch[0])
+            lens += out[9].cpu().tolist()
+    assert len(names) == 6 and min(lens) >= 5
+    for n, L in zip(names, lens):
+        sr, wav = wavfile.read(os.path.join(tcfg["path"]["result_path"], n + ".wav"))
+        assert sr == 22050 and wav.dtype == np.float32 and wav.shape == (256 * (L - 2),) and np.isfinite(wav).all()
