@@ -120,12 +120,14 @@ extern "C" int fs2_rowvec_bwd(const void* dy, float* dtable, const int64_t* idx,
 }
 
 // ------------------------------------------------------------------ bucketize (right=False) + embedding add
-// idx = #{bins[i] < v}  == first i with bins[i] >= v   (torch.bucketize default; reference probe P3).
+// idx = first i with bins[i] >= v, nb if none   (torch.bucketize default; reference probe P3).  Written as !(bins >= v) rather
+// than bins < v so that a NaN value lands in the last bucket, nb, as torch.bucketize puts it (bins < NaN is false for every bin,
+// which sent NaN to bucket 0 - tests/test_elem_gpu.py::test_bucket_embed_fwd_edges).
 __device__ __forceinline__ int bucketize_lb(const float* __restrict__ bins, int nb, float v) {
     int lo = 0, hi = nb;
     while (lo < hi) {
         int mid = (lo + hi) >> 1;
-        if (bins[mid] < v) lo = mid + 1; else hi = mid;
+        if (!(bins[mid] >= v)) lo = mid + 1; else hi = mid;
     }
     return lo;
 }

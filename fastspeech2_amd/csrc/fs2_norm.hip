@@ -804,8 +804,9 @@ static void bn_slab_sum(const BnArgs& a, dim3 grid, int C, float* acc_dbeta, flo
 #define BN_REDUCE_CBLK 64          /* channels per workgroup of the reducing modes */
 #define BN_BWD1_BLOCKS 256         /* backward sums: tanh + dropout hash per element -> needs every CU */
 
-// stats[0..C) = sum, stats[C..2C) = sum of squared deviations.  `stats` is a workspace of fs2_bn_ws_floats(C) floats whose
-// counter words are zero on entry (zero the whole workspace once, when it is allocated; the kernels leave them zero).
+// stats[0..C) = sum, stats[C..2C) = sum of squared deviations.  `stats` is a workspace of fs2_bn_ws_floats(C) floats laid out as
+// [2C sums][BN_WS_ROWS x 2C slab]; it needs no initial contents: every slab row the summing launch reads (row groups 0 .. grid.x - 1,
+// all 2C columns) is written by the statistics launch before it (tests/test_elem_gpu.py fills the workspace with NaN first).
 extern "C" int fs2_bn_stats(const void* x, float* stats, long ws_floats, int M, int C, int dtype, hipStream_t stream) {
     FS2_CHECK_ARG(x && stats, "bn_stats: null pointer");
     FS2_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && C <= 1024, "bn_stats: bad shape M=%d C=%d", M, C);
@@ -843,7 +844,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, const float*
 }
 // Train-mode statistics in two launches and no housekeeping: shifted sums (MODE 0) -> ONE kernel that converts them, updates
 // the running statistics, writes mean / rstd and counts the batch (nn.BatchNorm1d.num_batches_tracked).  The workspace
-// (fs2_bn_ws_floats(C) floats) is zeroed once by the caller, when it allocates it.
+// (fs2_bn_ws_floats(C) floats) needs no initial contents: the statistics launch writes every slab row this kernel reads.
 template <typename T>
 __global__ void bn_fix_finalize_kernel(const T* __restrict__ x, float* __restrict__ stats, float* __restrict__ running_mean,
                                        float* __restrict__ running_var, long long* __restrict__ nbt, float* __restrict__ mean_rstd,
@@ -919,7 +920,7 @@ extern "C" int fs2_bn_apply(const void* x, const float* mean_rstd, const float* 
 
 // Backward, pass 1: g = dout * dropmask * act'(.)  ;  sums[c] += g, sums[C+c] += g*xhat  (also = dbeta, dgamma)
 //           pass 2: dx = gamma*rstd*(g - sums[c]/M - xhat*sums[C+c]/M)
-// sums (a workspace of fs2_bn_ws_floats(C) floats, counter words zero on entry) receives dbeta (first C) and dgamma (next C).
+// sums (a workspace of fs2_bn_ws_floats(C) floats, any contents on entry: see fs2_bn_stats) receives dbeta (first C) and dgamma (next C).
 extern "C" int fs2_bn_bwd(const void* x, const void* dout, const float* mean_rstd, const float* gamma, const float* beta,
                           float* sums, long ws_floats, void* dx, int M, int C, int act, float p, uint64_t seed, const uint64_t* seed_dev,
                           int dtype, hipStream_t stream) {

@@ -342,7 +342,7 @@ def ln_bwd_reduce(ws, C, dgamma, dbeta):
 # ------------------------------------------------------------------ batch norm
 def bn_train_fwd(x, gamma, beta, running_mean, running_var, act, p, seed, eps=1e-5, momentum=0.1, res=None, seed_dev=None,
                  ws=None, num_batches_tracked=None):
-    """ws: a persistent BN workspace (bn_workspace(C): zeroed once, kept consistent by the kernels): statistics, running-stat
+    """ws: a persistent BN workspace (bn_workspace(C), reused by every call of width C: each call writes every slab word it reads): statistics, running-stat
     update and the num_batches_tracked increment then take two launches, with no fill / fix-up / counter launches around them."""
     M, C = x.shape
     mean_rstd = torch.empty(2 * C, device=x.device, dtype=torch.float32)
