@@ -18,6 +18,7 @@ _CTYPES = {
     "int": ctypes.c_int,
     "long": ctypes.c_long,
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
     "uint64_t": ctypes.c_uint64,
     "size_t": ctypes.c_size_t,
     "fs2_stream_t": ctypes.c_void_p,

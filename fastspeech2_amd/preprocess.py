@@ -9,6 +9,8 @@ processed in two stages so that the GPU sees few, large launches:
 
   host stage    per utterance: TextGrid -> phones / frame durations / trim window (`get_alignment`), wav read + trim,
                 F0 (pyworld DIO + StoneMask when importable, or a caller-supplied `pitch_fn`); thread pool.
+                With `pitch="gpu"` F0 moves to the device stage instead: `pitch.dio_stonemask` on each ragged batch of the
+                unclipped trimmed audio (csrc/fs2_f0.hip).
   device stage  utterances are packed, longest first, into ragged batches of up to `batch_seconds` of audio
                 (one pinned staging buffer -> one H2D copy -> reflect pad per row -> framed-DFT GEMM -> fused
                 |.| / mel / log / energy epilogue -> one D2H copy), `audio.TacotronSTFT.mel_spectrogram_ragged`.
@@ -24,7 +26,8 @@ Third-party pieces of the reference that are absent from this image and what sta
   librosa==0.7.2 `load`          -> `load_wav`: scipy.io.wavfile, mono, float32 in [-1, 1); polyphase resampling to
                                     22050 Hz only if the file's rate differs (librosa.load's default sr; the files
                                     `prepare_align.py` writes are already at that rate)
-  pyworld==0.2.10 dio/stonemask  -> imported when present; otherwise `pitch_fn` must be given (no silent substitute)
+  pyworld==0.2.10 dio/stonemask  -> imported when present; otherwise `pitch_fn` or `pitch="gpu"` (DIO + StoneMask as HIP
+                                    kernels, fastspeech2_amd/pitch.py) must be given (no silent substitute)
   sklearn StandardScaler         -> `RunningMoments` (the same incremental mean/variance update, Chan et al.)
 """
 import json
@@ -193,12 +196,29 @@ def _pyworld_pitch():
     return pitch_fn
 
 
+def resolve_pitch(choice):
+    """preprocess.py --pitch: "pyworld" -> None (the host pyworld path), "gpu" -> "gpu", "auto" -> pyworld when importable,
+    else "gpu".  The result is Preprocessor's `pitch` keyword."""
+    if choice not in ("auto", "pyworld", "gpu"):
+        raise ValueError(f"--pitch must be auto, pyworld or gpu, got {choice!r}")
+    if choice == "auto":
+        return None if _pyworld_pitch() is not None else "gpu"
+    return None if choice == "pyworld" else "gpu"
+
+
 # ------------------------------------------------------------------------------------------------ the preprocessor
 class Preprocessor:
-    def __init__(self, config, device="cuda", pitch_fn=None, batch_seconds=1800.0, num_workers=8, seed=None):
+    def __init__(self, config, device="cuda", pitch_fn=None, batch_seconds=1800.0, num_workers=8, seed=None, pitch=None):
         """`config` = preprocess.yaml (preprocessor.py:16-51).  `pitch_fn(wav float32, sampling_rate, hop_length) -> f0 per
-        frame (0 = unvoiced)` replaces pyworld when that package is absent; `seed` fixes the train/val shuffle
-        (the reference uses the unseeded global `random`)."""
+        frame (0 = unvoiced)` replaces pyworld when that package is absent; `pitch="gpu"` computes F0 on the GPU per ragged
+        batch instead (fastspeech2_amd.pitch); `seed` fixes the train/val shuffle (the reference uses the unseeded global
+        `random`)."""
+        if pitch not in (None, "gpu"):
+            raise ValueError(f"pitch must be None or 'gpu', got {pitch!r}")
+        if pitch == "gpu" and pitch_fn is not None:
+            raise ValueError("pass either pitch_fn or pitch='gpu', not both")
+        if pitch == "gpu" and torch.device(device).type != "cuda":
+            raise RuntimeError("Preprocessor(pitch='gpu') runs DIO + StoneMask on an AMD GPU only (no CPU fallback)")
         self.config = config
         self.in_dir = config["path"]["raw_path"]
         self.out_dir = config["path"]["preprocessed_path"]
@@ -218,11 +238,13 @@ class Preprocessor:
             config["preprocessing"]["mel"]["mel_fmax"])
         self.device = torch.device(device)
         self.pitch_fn = pitch_fn
+        self.pitch = pitch
         self.batch_samples = int(batch_seconds * self.sampling_rate)
         self.num_workers = num_workers
         self.host_chunk = max(64, 8 * num_workers)          # utterances handed to the host thread pool at a time
         self.seed = seed
         self._staging = None
+        self._pitch_staging = None
 
     # ---------------------------------------------------------------- host stage
     def get_alignment(self, intervals):
@@ -259,9 +281,11 @@ class Preprocessor:
         wav = wav[int(self.sampling_rate * start):int(self.sampling_rate * end)].astype(np.float32)
         with open(os.path.join(self.in_dir, speaker, "{}.lab".format(basename)), "r") as f:
             raw_text = f.readline().strip("\n")
-        pitch = np.asarray(self.pitch_fn(wav, self.sampling_rate, self.hop_length), dtype=np.float64)[:sum(duration)]
-        if np.sum(pitch != 0) <= 1:
-            return None
+        pitch = None                                                        # pitch="gpu": set by the device stage
+        if self.pitch != "gpu":
+            pitch = np.asarray(self.pitch_fn(wav, self.sampling_rate, self.hop_length), dtype=np.float64)[:sum(duration)]
+            if np.sum(pitch != 0) <= 1:
+                return None
         return {"speaker": speaker, "basename": basename, "text": "{" + " ".join(phone) + "}", "raw_text": raw_text,
                 "duration": duration, "wav": wav, "pitch": pitch}
 
@@ -300,6 +324,21 @@ class Preprocessor:
         return [(mel[b, :, :f].astype(np.float32), energy[b, :f].astype(np.float32))
                 for b, f in enumerate(frames.tolist())]
 
+    def _extract_pitch(self, wavs):
+        """pitch="gpu": [float32 1-D] -> [f0 per DIO frame, float64], DIO + StoneMask on the GPU over the UNCLIPPED audio (the
+        reference's pitch_fn sees the wav before get_mel_from_wav clips it); its own staging buffer, one H2D and one D2H copy."""
+        from . import pitch as Pitch
+        lens = [len(w) for w in wavs]
+        B, N = len(wavs), max(lens)
+        if self._pitch_staging is None or self._pitch_staging.numel() < B * N:
+            self._pitch_staging = torch.empty(B * N, dtype=torch.float32).pin_memory()
+        hv = self._pitch_staging[:B * N].view(B, N)
+        for b, w in enumerate(wavs):
+            hv.numpy()[b, :lens[b]] = w
+        f0, _, frames = Pitch.dio_stonemask(hv.to(self.device, non_blocking=True), lens, self.sampling_rate,
+                                            self.hop_length / self.sampling_rate * 1000)
+        return [f0[b, :f] for b, f in enumerate(frames.tolist())]
+
     # ---------------------------------------------------------------- per utterance, after the STFT
     def _finish_utterance(self, it, mel_spectrogram, energy):
         """preprocessor.py:194-241."""
@@ -336,10 +375,11 @@ class Preprocessor:
 
     # ---------------------------------------------------------------- the corpus pass
     def build_from_path(self):
-        if self.pitch_fn is None:
+        if self.pitch_fn is None and self.pitch != "gpu":
             self.pitch_fn = _pyworld_pitch()
-        if self.pitch_fn is None:
-            raise RuntimeError("pyworld is not installed: pass pitch_fn=(wav, sampling_rate, hop_length) -> f0 per frame")
+        if self.pitch_fn is None and self.pitch != "gpu":
+            raise RuntimeError("pyworld is not installed: pass pitch_fn=(wav, sampling_rate, hop_length) -> f0 per frame, "
+                               "or pitch=\"gpu\" for DIO + StoneMask on the GPU")
         for d in ("mel", "pitch", "energy", "duration"):
             os.makedirs(os.path.join(self.out_dir, d), exist_ok=True)
         print("Processing Data ...")
@@ -363,8 +403,15 @@ class Preprocessor:
         def flush():
             items = [it for _, it in window]
             for batch in self._batches(items):
-                for i, (mel, energy) in zip(batch, self._extract_mels([items[i]["wav"] for i in batch])):
+                wavs = [items[i]["wav"] for i in batch]
+                pitches = self._extract_pitch(wavs) if self.pitch == "gpu" else None
+                for j, (i, (mel, energy)) in enumerate(zip(batch, self._extract_mels(wavs))):
                     items[i]["wav"] = None                                  # release the audio once its features exist
+                    if pitches is not None:                                 # _host_stage's trim and voiced-frame rule
+                        items[i]["pitch"] = pitches[j][:sum(items[i]["duration"])]
+                        if np.sum(items[i]["pitch"] != 0) <= 1:
+                            results[window[i][0]] = None
+                            continue
                     results[window[i][0]] = self._finish_utterance(items[i], mel, energy)
             window.clear()
 

@@ -320,6 +320,32 @@ int fs2_gl_ola(const float* seg, long lds, const int32_t* frames, const double* 
 /* stft.py:74-81: ft rows -> magnitude, phase = atan2(Im, Re), each (B, NF, F) */
 int fs2_gl_mag_phase(const float* ft, long ldft, int S, float* mag, float* phase, int B, int F, int NF, fs2_stream_t stream);
 
+/* ---- F0: DIO + StoneMask (reference preprocessor/preprocessor.py:182-187; specification: fastspeech2_amd/pitch.py) ----
+ * fp64 throughout; rows x[b][0, lens[b]) of a float32 batch (row stride ldx), nothing beyond lens[b] is read; fixed-order reductions,
+ * no atomics: a row's F0 does not depend on the rest of its batch.  Frame-major outputs [B][Fmax], frames[b] valid per row.
+ * fs2_f0_dc: stats[b] = {mean over N+1 samples (x[N] := 0), event threshold 1e-9 max|x - mean|}. */
+int fs2_f0_dc(const float* x, long ldx, const int32_t* lens, double* stats, int B, int Nmax, fs2_stream_t stream);
+/* zero-phase 50 Hz low-cut of the DC-free row: lc[b][m + H] for m in [-H, N + H], taps[2R + 1] (ldl >= Nmax + 2H + 1) */
+int fs2_f0_lowcut(const float* x, long ldx, const int32_t* lens, const double* stats, const double* taps, int R, double* lc,
+                  long ldl, int H, int B, int Nmax, fs2_stream_t stream);
+/* per band (nuttall: the nb bands' 4 band_h[j] low-pass taps back to back): band signal -> negative-going, positive-going, peak and
+ * dip events.  emit = 0: counts[B][nb][4][ceil(Nmax / 256)] per tile; emit = 1: positions at offs into events[B][nb][4][cap]. */
+int fs2_f0_events(const double* lc, long ldl, int H, const int32_t* lens, const double* stats, const double* nuttall,
+                  const int32_t* band_h, int nb, int max_h, int32_t* counts, const int32_t* offs, double* events, long cap, int B,
+                  int Nmax, int emit, fs2_stream_t stream);
+/* exclusive prefix of the tile counts per (row, band, stream) -> offs, totals[B][nb][4] */
+int fs2_f0_scan(const int32_t* counts, int32_t* offs, int32_t* totals, int B, int nb, int Nmax, fs2_stream_t stream);
+/* per (frame, band): candidate F0 and normalised score cand / score [B][nb][Fmax] from the four event lists */
+int fs2_f0_candidates(const double* events, long cap, const int32_t* totals, const int32_t* frames, const double* band_f0,
+                      int nb, double fs, double frame_period, double f0_floor, double f0_ceil, double* cand, double* score,
+                      int B, int Fmax, fs2_stream_t stream);
+/* best band per frame and contour fixing steps 1-4 (vrm: voice range minimum in frames; tmp [B][2][Fmax]) -> f0 [B][Fmax] */
+int fs2_f0_fix(const double* cand, const double* score, const int32_t* frames, int nb, int vrm, double allowed_range,
+               double* tmp, double* f0, int B, int Fmax, fs2_stream_t stream);
+/* StoneMask refinement of f0 [B][Fmax] at t = f frame_period / 1000 from the DC-intact rows -> out (may alias f0) */
+int fs2_f0_stonemask(const float* x, long ldx, const int32_t* lens, const double* f0, const int32_t* frames, double fs,
+                     double frame_period, double* out, int B, int Fmax, int Nmax, fs2_stream_t stream);
+
 /* ---- loss (model/loss.py:19-92): masked L1 (mel, post-net mel) + masked MSE (pitch, energy, log-duration) ----
  * mel / post: [B][T][n_mel] f32 predictions; mel_t: target with batch stride ld_t_b (its own padded length >= T);
  * lens int64 (valid = t < min(len, T)); p/e predictions [B][L] (phoneme level) or [B][T] (p_frame / e_frame = 1) with

@@ -5,7 +5,7 @@ import argparse
 
 import yaml
 
-from fastspeech2_amd.preprocess import Preprocessor
+from fastspeech2_amd.preprocess import Preprocessor, resolve_pitch
 
 if __name__ == "__main__":
     parser = argparse.ArgumentParser()
@@ -13,11 +13,14 @@ if __name__ == "__main__":
     parser.add_argument("--batch_seconds", type=float, default=1800.0, help="audio per ragged STFT batch on the GPU")
     parser.add_argument("--num_workers", type=int, default=8, help="host threads for TextGrid / wav / F0")
     parser.add_argument("--seed", type=int, default=None, help="seed of the train/val shuffle (reference: unseeded)")
+    parser.add_argument("--pitch", choices=["auto", "pyworld", "gpu"], default="auto",
+                        help="F0: pyworld on the host, or DIO + StoneMask on the GPU; auto = pyworld when importable, else gpu")
     parser.add_argument("--pack", action="store_true", help="also write the packed feature shards for train.txt / val.txt")
     args = parser.parse_args()
 
     config = yaml.load(open(args.config, "r"), Loader=yaml.FullLoader)
-    Preprocessor(config, batch_seconds=args.batch_seconds, num_workers=args.num_workers, seed=args.seed).build_from_path()
+    Preprocessor(config, batch_seconds=args.batch_seconds, num_workers=args.num_workers, seed=args.seed,
+                 pitch=resolve_pitch(args.pitch)).build_from_path()
     if args.pack:
         from fastspeech2_amd.data import pack_features
         for split in ("train.txt", "val.txt"):
