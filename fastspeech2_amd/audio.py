@@ -20,6 +20,9 @@ The other half, spectrogram -> audio (audio/stft.py:15-122 STFT, audio/audio_pro
 run on the same exact-fp32 MFMA GEMM (the framed DFT above; the inverse as a one-tap GEMM of frames x inverse_basis into
 per-frame segments); the phase projection and the overlap-add with the window_sumsquare division are
 csrc/fs2_griffin_lim.hip.  One iteration = 4 launches on the current stream, buffers sized once per call.
+
+Sample-rate conversion and peak normalisation of ragged batches (`resample_poly`, `peak_abs`, `peaknorm_pcm`) live in
+fastspeech2_amd/resample.py and are re-exported here.
 """
 import functools
 
@@ -27,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .resample import peak_abs, peaknorm_pcm, resample_poly  # noqa: F401
 
 
 def slaney_mel_filterbank(sr, n_fft, n_mels, fmin, fmax):

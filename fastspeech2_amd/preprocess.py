@@ -11,9 +11,15 @@ processed in two stages so that the GPU sees few, large launches:
                 F0 (pyworld DIO + StoneMask when importable, or a caller-supplied `pitch_fn`); thread pool.
                 With `pitch="gpu"` F0 moves to the device stage instead: `pitch.dio_stonemask` on each ragged batch of the
                 unclipped trimmed audio (csrc/fs2_f0.hip).
+                With `resample="gpu"` a file whose rate differs from the config's is no longer resampled here: the wav stays at
+                its own rate, the trim window is computed in OUTPUT samples exactly as above, and only the input span that
+                window depends on goes to the device stage.
   device stage  utterances are packed, longest first, into ragged batches of up to `batch_seconds` of audio
                 (one pinned staging buffer -> one H2D copy -> reflect pad per row -> framed-DFT GEMM -> fused
                 |.| / mel / log / energy epilogue -> one D2H copy), `audio.TacotronSTFT.mel_spectrogram_ragged`.
+                With `resample="gpu"` batches hold one source rate and start with `resample.resample_poly` of each row's trim
+                window (csrc/fs2_resample.hip): its unclipped output feeds `pitch.dio_stonemask`, its clamped output the STFT,
+                without a round trip through the host.
 
 Everything after the device stage (trim to sum(duration), phoneme-level averaging, outlier removal for the statistics,
 normalisation, file formats, metadata lines, the train/val split) follows the reference line by line, including
@@ -113,8 +119,9 @@ def read_textgrid(path, include_empty_intervals=False):
 
 
 # ------------------------------------------------------------------------------------------------ small host pieces
-def load_wav(path, target_sr=22050):
-    """float32 mono waveform at `target_sr` (what `librosa.load(path)` returns for the reference, preprocessor.py:172)."""
+def load_wav(path, target_sr=22050, resample=True):
+    """float32 mono waveform at `target_sr` (what `librosa.load(path)` returns for the reference, preprocessor.py:172).
+    `resample=False` leaves the file at its own rate and returns (waveform, rate) for a caller that resamples on the GPU."""
     from scipy.io import wavfile
 
     sr, w = wavfile.read(path)
@@ -126,6 +133,8 @@ def load_wav(path, target_sr=22050):
         w = w.astype(np.float32)
     if w.ndim == 2:
         w = w.mean(axis=1)
+    if not resample:
+        return w, int(sr)
     if sr != target_sr:
         from math import gcd
         from scipy.signal import resample_poly
@@ -208,11 +217,18 @@ def resolve_pitch(choice):
 
 # ------------------------------------------------------------------------------------------------ the preprocessor
 class Preprocessor:
-    def __init__(self, config, device="cuda", pitch_fn=None, batch_seconds=1800.0, num_workers=8, seed=None, pitch=None):
+    def __init__(self, config, device="cuda", pitch_fn=None, batch_seconds=1800.0, num_workers=8, seed=None, pitch=None,
+                 resample=None):
         """`config` = preprocess.yaml (preprocessor.py:16-51).  `pitch_fn(wav float32, sampling_rate, hop_length) -> f0 per
         frame (0 = unvoiced)` replaces pyworld when that package is absent; `pitch="gpu"` computes F0 on the GPU per ragged
         batch instead (fastspeech2_amd.pitch); `seed` fixes the train/val shuffle (the reference uses the unseeded global
-        `random`)."""
+        `random`); `resample="gpu"` converts files at another rate than the config's on the GPU, per ragged batch, instead of
+        per file in `load_wav` (needs `pitch="gpu"`: a host pitch backend would need the audio back on the host)."""
+        if resample not in (None, "gpu"):
+            raise ValueError(f"resample must be None or 'gpu', got {resample!r}")
+        if resample == "gpu" and pitch != "gpu":
+            raise ValueError("resample='gpu' needs pitch='gpu': with a host pitch backend the resampled audio would have to come "
+                             "back to the host")
         if pitch not in (None, "gpu"):
             raise ValueError(f"pitch must be None or 'gpu', got {pitch!r}")
         if pitch == "gpu" and pitch_fn is not None:
@@ -239,6 +255,7 @@ class Preprocessor:
         self.device = torch.device(device)
         self.pitch_fn = pitch_fn
         self.pitch = pitch
+        self.resample = resample
         self.batch_samples = int(batch_seconds * self.sampling_rate)
         self.num_workers = num_workers
         self.host_chunk = max(64, 8 * num_workers)          # utterances handed to the host thread pool at a time
@@ -277,8 +294,19 @@ class Preprocessor:
         phone, duration, start, end = self.get_alignment(tiers["phones"])
         if start >= end:
             return None
-        wav = load_wav(os.path.join(self.in_dir, speaker, "{}.wav".format(basename)))
-        wav = wav[int(self.sampling_rate * start):int(self.sampling_rate * end)].astype(np.float32)
+        window = {}
+        if self.resample == "gpu":                                          # the same window, in samples of the resampled file
+            from . import resample as R
+            full, sr = load_wav(os.path.join(self.in_dir, speaker, "{}.wav".format(basename)), resample=False)
+            up, down = R.ratio(sr, self.sampling_rate)
+            n_out = R.out_length(len(full), up, down)
+            a, e = min(int(self.sampling_rate * start), n_out), min(int(self.sampling_rate * end), n_out)
+            lo, hi = R.input_span(a, e - a, len(full), up, down)
+            wav = full[lo:hi].astype(np.float32)
+            window = {"sr": sr, "in_begin": lo, "out_begin": a, "out_len": max(e - a, 0)}
+        else:
+            wav = load_wav(os.path.join(self.in_dir, speaker, "{}.wav".format(basename)))
+            wav = wav[int(self.sampling_rate * start):int(self.sampling_rate * end)].astype(np.float32)
         with open(os.path.join(self.in_dir, speaker, "{}.lab".format(basename)), "r") as f:
             raw_text = f.readline().strip("\n")
         pitch = None                                                        # pitch="gpu": set by the device stage
@@ -287,7 +315,7 @@ class Preprocessor:
             if np.sum(pitch != 0) <= 1:
                 return None
         return {"speaker": speaker, "basename": basename, "text": "{" + " ".join(phone) + "}", "raw_text": raw_text,
-                "duration": duration, "wav": wav, "pitch": pitch}
+                "duration": duration, "wav": wav, "pitch": pitch, **window}
 
     # ---------------------------------------------------------------- device stage
     def _batches(self, items):
@@ -303,6 +331,16 @@ class Preprocessor:
             longest = max(longest, n)
         if batch:
             yield batch
+
+    def _rate_batches(self, items):
+        """resample="gpu": `_batches` within each source rate (one filter per launch)."""
+        by_rate = {}
+        for i, it in enumerate(items):
+            by_rate.setdefault(it["sr"], []).append(i)
+        for sr in sorted(by_rate):
+            idx = by_rate[sr]
+            for batch in self._batches([items[i] for i in idx]):
+                yield [idx[k] for k in batch]
 
     def _extract_mels(self, wavs):
         """[float32 1-D] -> [(mel (n_mel, frames), energy (frames,))] float32 numpy; one ragged launch set on the GPU
@@ -338,6 +376,29 @@ class Preprocessor:
         f0, _, frames = Pitch.dio_stonemask(hv.to(self.device, non_blocking=True), lens, self.sampling_rate,
                                             self.hop_length / self.sampling_rate * 1000)
         return [f0[b, :f] for b, f in enumerate(frames.tolist())]
+
+    def _extract_resampled(self, its):
+        """resample="gpu": host-stage items of ONE source rate -> ([f0 per DIO frame], [(mel, energy)]).  One H2D copy of the input
+        spans, `resample_poly` of each row's trim window, then F0 on its unclipped and the STFT on its clamped output."""
+        from . import pitch as Pitch, resample as R
+        if self.device.type != "cuda":
+            raise RuntimeError("fastspeech2_amd.preprocess runs its STFT on an AMD GPU only (no CPU fallback)")
+        lens = [len(it["wav"]) for it in its]
+        B, N = len(its), max(max(lens), 1)
+        if self._staging is None or self._staging.numel() < B * N:
+            self._staging = torch.empty(B * N, dtype=torch.float32).pin_memory()
+        host = self._staging[:B * N].view(B, N)
+        hv = host.numpy()
+        for b, it in enumerate(its):
+            hv[b, :lens[b]] = it["wav"]
+        y, yc, out_lens = R.resample_poly(host.to(self.device, non_blocking=True), lens, its[0]["sr"], self.sampling_rate,
+                                          out_begin=[it["out_begin"] for it in its], out_len=[it["out_len"] for it in its],
+                                          clip=True, in_begin=[it["in_begin"] for it in its])
+        f0, _, f0_frames = Pitch.dio_stonemask(y, out_lens, self.sampling_rate, self.hop_length / self.sampling_rate * 1000)
+        mel, energy, frames = self.STFT.mel_spectrogram_ragged(yc, out_lens.to(torch.int32))
+        mel, energy = mel.cpu().numpy(), energy.cpu().numpy()
+        return ([f0[b, :f] for b, f in enumerate(f0_frames.tolist())],
+                [(mel[b, :, :f].astype(np.float32), energy[b, :f].astype(np.float32)) for b, f in enumerate(frames.tolist())])
 
     # ---------------------------------------------------------------- per utterance, after the STFT
     def _finish_utterance(self, it, mel_spectrogram, energy):
@@ -402,10 +463,14 @@ class Preprocessor:
 
         def flush():
             items = [it for _, it in window]
-            for batch in self._batches(items):
-                wavs = [items[i]["wav"] for i in batch]
-                pitches = self._extract_pitch(wavs) if self.pitch == "gpu" else None
-                for j, (i, (mel, energy)) in enumerate(zip(batch, self._extract_mels(wavs))):
+            for batch in (self._rate_batches(items) if self.resample == "gpu" else self._batches(items)):
+                if self.resample == "gpu":
+                    pitches, mels = self._extract_resampled([items[i] for i in batch])
+                else:
+                    wavs = [items[i]["wav"] for i in batch]
+                    pitches = self._extract_pitch(wavs) if self.pitch == "gpu" else None
+                    mels = self._extract_mels(wavs)
+                for j, (i, (mel, energy)) in enumerate(zip(batch, mels)):
                     items[i]["wav"] = None                                  # release the audio once its features exist
                     if pitches is not None:                                 # _host_stage's trim and voiced-frame rule
                         items[i]["pitch"] = pitches[j][:sum(items[i]["duration"])]

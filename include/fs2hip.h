@@ -320,6 +320,26 @@ int fs2_gl_ola(const float* seg, long lds, const int32_t* frames, const double* 
 /* stft.py:74-81: ft rows -> magnitude, phase = atan2(Im, Re), each (B, NF, F) */
 int fs2_gl_mag_phase(const float* ft, long ldft, int S, float* mag, float* phase, int B, int F, int NF, fs2_stream_t stream);
 
+/* ---- sample-rate conversion and peak normalisation (reference preprocessor/ljspeech.py:28-34: librosa.load(path, sr), then
+ * wav / max|wav| * max_wav_value as int16; specification: fastspeech2_amd/resample.py) ----
+ * fs2_resample_poly: rational polyphase resampler over a ragged float32 batch.  Row b of x (row stride ldx) holds in_len[b]
+ * samples that start at absolute input index in_begin[b] of its utterance (in_begin == NULL: 0); every other input index counts as
+ * zero and nothing beyond in_len[b] is read.  Outputs j in [out_begin[b], out_begin[b] + out_len[b]) (out_begin == NULL: 0) go to
+ * y[b][j - out_begin[b]] (row stride ldy), and clamped to [-1, 1] to yc (optional, same stride):
+ *     y[j] = sum_{s < T} tab[p][s] * x[q - T + 1 + s],   p = (j down + half) mod up,   q = (j down + half) div up,
+ * tab [up][T] the fp64 taps phase-major in ascending input index (T even, 16-byte aligned; fastspeech2_amd.resample.phase_table).
+ * fp64 fma in ascending s, one rounding to float32; no atomics; a row's result does not depend on its batch. */
+int fs2_resample_poly(const float* x, long ldx, const int32_t* in_begin, const int32_t* in_len, const double* tab, int up,
+                      int down, int half, int T, const int32_t* out_begin, const int32_t* out_len, float* y, float* yc, long ldy,
+                      int B, int Nin, int Nout, fs2_stream_t stream);
+/* peak[b] = max |y[b][0, lens[b])| (0 for an empty row; exact in any order, NaN propagates) */
+int fs2_peak_abs(const float* y, long ldy, const int32_t* lens, float* peak, int B, int Nmax, fs2_stream_t stream);
+/* pcm[b][n] = (int16)(y[b][n] / peak[b] * max_wav_value): float32 division then product, numpy's astype semantics (truncate toward
+ * zero to int32, low 16 bits: a positive peak sample times 32768 becomes -32768, as in the reference).  peak[b] == 0: zeros;
+ * [lens[b], Nmax) of a row is zero-filled. */
+int fs2_peaknorm_pcm(const float* y, long ldy, const int32_t* lens, const float* peak, float max_wav_value, int16_t* pcm, long ldp,
+                     int B, int Nmax, fs2_stream_t stream);
+
 /* ---- F0: DIO + StoneMask (reference preprocessor/preprocessor.py:182-187; specification: fastspeech2_amd/pitch.py) ----
  * fp64 throughout; rows x[b][0, lens[b]) of a float32 batch (row stride ldx), nothing beyond lens[b] is read; fixed-order reductions,
  * no atomics: a row's F0 does not depend on the rest of its batch.  Frame-major outputs [B][Fmax], frames[b] valid per row.

@@ -15,12 +15,15 @@ if __name__ == "__main__":
     parser.add_argument("--seed", type=int, default=None, help="seed of the train/val shuffle (reference: unseeded)")
     parser.add_argument("--pitch", choices=["auto", "pyworld", "gpu"], default="auto",
                         help="F0: pyworld on the host, or DIO + StoneMask on the GPU; auto = pyworld when importable, else gpu")
+    parser.add_argument("--resample", choices=["host", "gpu"], default="host",
+                        help="files at another rate than the config's: polyphase resampling per file on the host, or per ragged "
+                             "batch on the GPU (needs the GPU pitch backend)")
     parser.add_argument("--pack", action="store_true", help="also write the packed feature shards for train.txt / val.txt")
     args = parser.parse_args()
 
     config = yaml.load(open(args.config, "r"), Loader=yaml.FullLoader)
     Preprocessor(config, batch_seconds=args.batch_seconds, num_workers=args.num_workers, seed=args.seed,
-                 pitch=resolve_pitch(args.pitch)).build_from_path()
+                 pitch=resolve_pitch(args.pitch), resample="gpu" if args.resample == "gpu" else None).build_from_path()
     if args.pack:
         from fastspeech2_amd.data import pack_features
         for split in ("train.txt", "val.txt"):
