@@ -1,0 +1,29 @@
+"""`python align.py config/LJSpeech/preprocess.yaml` — forced alignment on the GPU in place of the Montreal Forced Aligner run the
+reference's README asks for: trains a monophone HMM on `raw_path`'s wav + .lab pairs with `path.lexicon_path` and writes
+`{preprocessed_path}/TextGrid/{speaker}/{basename}.TextGrid` for preprocess.py (fastspeech2_amd/align.py)."""
+import argparse
+import sys
+
+import yaml
+
+from fastspeech2_amd.align import build
+
+if __name__ == "__main__":
+    parser = argparse.ArgumentParser()
+    parser.add_argument("config", type=str, help="path to preprocess.yaml")
+    parser.add_argument("--states", type=int, default=2, help="HMM states per phone (1..3)")
+    parser.add_argument("--iters", type=int, default=12, help="Baum-Welch passes after the flat start")
+    parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
+    parser.add_argument("--device", type=str, default="cuda")
+    parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
+    parser.add_argument("--num_workers", type=int, default=8, help="host threads reading wav and .lab files")
+    args = parser.parse_args()
+
+    config = yaml.load(open(args.config, "r"), Loader=yaml.FullLoader)
+    try:
+        written, skipped, history = build(config, device=args.device, states=args.states, iters=args.iters, overwrite=args.overwrite,
+                                          batch_bytes=int(args.batch_gib * (1 << 30)), num_workers=args.num_workers)
+    except FileExistsError as e:
+        sys.exit(str(e))
+    print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))
+    print("{} TextGrids written, {} utterances skipped".format(written, len(skipped)))

@@ -1,0 +1,551 @@
+"""Forced alignment on the GPU: a left-to-right monophone HMM trained with Baum-Welch on the corpus itself and decoded with Viterbi,
+writing the `{preprocessed_path}/TextGrid/{speaker}/{basename}.TextGrid` files that `Preprocessor` reads (the reference has no
+aligner: its README sends the user to a Montreal Forced Aligner 1.x binary).  HIP kernels in fp64 over ragged batches
+(csrc/fs2_align.hip).  The specification below is what the kernels and the numpy oracle (tests/align_ref.py) implement.  It is a
+textbook flat-start monophone system (Rabiner 1989; the first stage of every HMM aligner); nothing here has been measured against
+MFA, and the defaults marked "a choice" are choices, not measurements.
+
+Features.  m[c, t] is the log-mel spectrogram `audio.TacotronSTFT` gives with the config's STFT settings for the whole file (no trim),
+clamped to [-1, 1] first; T = samples // hop + 1 frames.  In float64 from here on: x[t, c] = m[c, t] - mean_t m[c, t] for c < n_mel,
+x[t, n_mel + c] = (x[min(t + 1, T - 1), c] - x[max(t - 1, 0), c]) / 2.  D = 2 n_mel (160).
+
+Lexicon and graph (host).  `path.lexicon_path` holds `word <blanks> phone phone ...` lines; the first pronunciation of a word wins and
+lookup is lower-cased (the reference's `read_lexicon`).  A .lab's first line loses its trailing punctuation and is split at blanks
+and at `, ; . - ? !` (synthesize.py `preprocess_english`); what is left of each piece after stripping punctuation from both ends is
+a word, empty pieces are dropped.  A word the lexicon does not know is the one-phone word `spn`.  Blocks, in order: optional `sil`,
+the phones of word 0, optional `sp`, the phones of word 1, ..., optional `sil`.  Every block has S states (1..3, default 2, a
+choice: at hop 256 / 22050 Hz the shortest phone is then 23 ms); state j = block * S + s has emission class phone_id * S + s.
+Predecessors of state j: j (self), j - 1 (next) and, when j is the first state of block k >= 2 and block k - 1 is optional, the last
+state of block k - 2 (skip).  A path starts in state 0 or, block 0 being optional, in state S; it ends in state J - 1 or, the last
+block being optional, in state J - 1 - S.  All arcs cost 0; transitions are not trained.  Per utterance: int32 arrays `sid`, `skip`
+(-1 where there is none) and `block` of length J, and `alt` = (S, J - 1 - S).  M = the states of the mandatory blocks; an utterance
+with T < M has no path: it is reported and skipped.  J above `max_states()` (1024) is a ValueError.
+
+Emissions.  One diagonal Gaussian per class: E[t, j] = -1/2 sum_d ((x_d - mu_d)^2 / var_d + log(2 pi var_d)), in the direct form,
+summed over d in ascending order (the kernel multiplies by 1 / var_d).
+
+Training.  Flat start: frame t of an utterance belongs to its mandatory state number (t M) // T (optional blocks get nothing); the
+first statistics are those of that hard assignment.  From their total the global mean g and variance v of the features follow;
+every class starts at (g, v), the variance floor is 1e-2 v, and the update below is applied.  Then `iters` passes (default 12, a
+choice).  A pass computes, per utterance, in the log domain (lse(a, b, c) = m + log(e^(a-m) + e^(b-m) + e^(c-m)), m the maximum, -inf
+if m is -inf):
+  alpha[0, j] = E[0, j] for the start states, else -inf;  alpha[t, j] = E[t, j] + lse(alpha[t-1, j], alpha[t-1, j-1], alpha[t-1, skip j])
+  loglik = lse over the end states of alpha[T-1, .], in index order
+  beta[T-1, j] = 0 for the end states, else -inf;  beta[t, j] = lse over the successors k = j, j + 1, the state that skips from j, of
+  E[t+1, k] + beta[t+1, k];  gamma[t, j] = exp(alpha[t, j] + beta[t, j] - loglik)
+and per class c the sums over all (utterance, state of class c) of  n = sum_t gamma,  a_d = sum_t gamma x_d,  q_d = sum_t gamma x_d^2.
+Update: a class with n >= 1 gets mu = a / n, var = max(q / n - mu^2, floor); one with n < 1 keeps its parameters.  A pass reports
+sum of loglik / sum of T, computed with the parameters it started from.
+
+Decoding.  Viterbi with the same arcs: delta[t, j] = E[t, j] + max over (self, next, skip), backpointer 0 / 1 / 2, the lowest code on
+ties; among the end states the lower index wins ties.  Backtracking gives frames per block; a skipped optional block has 0 frames
+and is not written.  Block boundaries are at f hop / sampling_rate seconds, f the cumulative frame count; the last one is xmax.
+
+Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
+sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
+update runs on the host in numpy.  Two runs over one corpus write byte-identical TextGrids.
+"""
+import os
+import re
+from concurrent.futures import ThreadPoolExecutor
+from string import punctuation
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+SIL, SP, SPN = "sil", "sp", "spn"
+VAR_FLOOR = 1e-2
+_SPLIT = re.compile(r"[,;.\-\?\!\s+]")
+
+
+# ------------------------------------------------------------------------------------------------ lexicon, text, graph
+def read_lexicon(path):
+    lexicon = {}
+    with open(path, encoding="utf-8") as f:
+        for line in f:
+            parts = line.split()
+            if parts and parts[0].lower() not in lexicon:
+                lexicon[parts[0].lower()] = parts[1:]
+    return lexicon
+
+
+def words_of(text):
+    """The words of one .lab line: trailing punctuation dropped, split as `preprocess_english` splits, punctuation stripped."""
+    pieces = (w.strip(punctuation) for w in _SPLIT.split(text.strip().rstrip(punctuation)))
+    return [w for w in pieces if w]
+
+
+def phone_table(lexicon):
+    """phone -> id over the lexicon's phones, sorted, then sil, sp, spn."""
+    phones = sorted({p for ps in lexicon.values() for p in ps} - {SIL, SP, SPN})
+    return {p: i for i, p in enumerate(phones + [SIL, SP, SPN])}
+
+
+def utterance_graph(words, lexicon, phone_ids, states=2):
+    """-> dict(sid, skip, block: int32 [J]; alt: (start, end) alternatives or -1; blocks: [(phone, word index or -1, optional)];
+    mandatory: number of states every path visits)."""
+    if not 1 <= states <= 3:
+        raise ValueError(f"states must be 1..3, got {states}")
+    if not words:
+        raise ValueError("an utterance needs at least one word")
+    blocks = [(SIL, -1, True)]
+    for w, word in enumerate(words):
+        if w:
+            blocks.append((SP, -1, True))
+        for p in lexicon.get(word.lower()) or [SPN]:
+            blocks.append((p, w, False))
+    blocks.append((SIL, -1, True))
+    S, J = states, len(blocks) * states
+    sid, skip, block = np.empty(J, np.int32), np.full(J, -1, np.int32), np.empty(J, np.int32)
+    for k, (p, _, _) in enumerate(blocks):
+        for s in range(S):
+            sid[k * S + s] = phone_ids[p] * S + s
+            block[k * S + s] = k
+        if k >= 2 and blocks[k - 1][2]:
+            skip[k * S] = (k - 1) * S - 1
+    alt = (S if blocks[0][2] else -1, J - 1 - S if blocks[-1][2] else -1)
+    return {"sid": sid, "skip": skip, "block": block, "alt": alt, "blocks": blocks,
+            "mandatory": S * sum(1 for b in blocks if not b[2])}
+
+
+def flat_assignment(graph, T):
+    """Flat start: the state of every frame, frame t -> mandatory state number (t M) // T."""
+    opt = np.array([b[2] for b in graph["blocks"]])
+    mand = np.nonzero(~opt[graph["block"]])[0]
+    return mand[(np.arange(T, dtype=np.int64) * len(mand)) // T]
+
+
+def m_step(sums, mu, var, floor):
+    """The update of the module docstring on class sums [C][1 + 2 D] -> (mu, var)."""
+    D = mu.shape[1]
+    n = sums[:, 0]
+    ok = n >= 1.0
+    nn = np.where(ok, n, 1.0)[:, None]
+    m = sums[:, 1:1 + D] / nn
+    v = np.maximum(sums[:, 1 + D:] / nn - m * m, floor[None, :])
+    return np.where(ok[:, None], m, mu), np.where(ok[:, None], v, var)
+
+
+# ------------------------------------------------------------------------------------------------ TextGrid
+def write_textgrid(path, words, phones, xmax):
+    """Long Praat text format, IntervalTiers `words` and `phones` of (start, end, text) intervals; times are written with repr, so
+    `preprocess.read_textgrid` returns them unchanged."""
+    def tier(i, name, items):
+        out = [f"    item [{i}]:", '        class = "IntervalTier"', f'        name = "{name}"', "        xmin = 0",
+               f"        xmax = {float(xmax)!r}", f"        intervals: size = {len(items)}"]
+        for k, (s, e, text) in enumerate(items, 1):
+            text = text.replace('"', '""')
+            out += [f"        intervals [{k}]:", f"            xmin = {float(s)!r}", f"            xmax = {float(e)!r}",
+                    f'            text = "{text}"']
+        return out
+    lines = ['File type = "ooTextFile"', 'Object class = "TextGrid"', "", "xmin = 0", f"xmax = {float(xmax)!r}", "tiers? <exists>",
+             "size = 2", "item []:"] + tier(1, "words", words) + tier(2, "phones", phones)
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def intervals(graph, words, frames, hop_length, sampling_rate):
+    """frames per block -> (words tier, phones tier, xmax): silences are "" in the words tier, zero-frame blocks are left out."""
+    t = lambda f: f * hop_length / sampling_rate                          # noqa: E731
+    ph, wd, f0 = [], [], 0
+    for (p, w, _), n in zip(graph["blocks"], frames):
+        n = int(n)
+        if n == 0:
+            continue
+        ph.append((t(f0), t(f0 + n), p))
+        if wd and w >= 0 and wd[-1][3] == w:
+            wd[-1] = (wd[-1][0], t(f0 + n), wd[-1][2], w)
+        else:
+            wd.append((t(f0), t(f0 + n), words[w] if w >= 0 else "", w))
+        f0 += n
+    return [x[:3] for x in wd], ph, t(f0)
+
+
+# ------------------------------------------------------------------------------------------------ kernels
+def max_states():
+    return _lib.load().fs2_align_max_states()
+
+
+def _dev(t, dtype, what, dim=3):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("fastspeech2_amd.align runs on an AMD GPU only (no CPU fallback): pass device tensors")
+    if t.dtype != dtype or t.dim() != dim or (t.numel() and t.stride(-1) != 1):
+        raise ValueError(f"{what} must be a {dim}-D {dtype} tensor with unit inner stride, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _lens(lens, B, cap, what, dev):
+    h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    if len(h) != B or any(n < 0 or n > cap for n in h):
+        raise ValueError(f"{what} must hold B={B} lengths in [0, {cap}], got {h}")
+    return h, torch.tensor(h, dtype=torch.int32, device=dev)
+
+
+class Graphs:
+    """The graphs of one ragged batch on the device: sid / skip / block [B][Jmax] int32 (-1 padded), alt [B][2], jlens."""
+
+    def __init__(self, graphs, device):
+        self.graphs = graphs
+        self.jl = [len(g["sid"]) for g in graphs]
+        self.Jmax = max(self.jl) if graphs else 0
+        if self.Jmax > max_states():
+            raise ValueError(f"an utterance of {self.Jmax} states exceeds the supported maximum of {max_states()}")
+        self.nbmax = max((len(g["blocks"]) for g in graphs), default=0)
+        packed = np.full((3, len(graphs), max(self.Jmax, 1)), -1, np.int32)
+        for b, g in enumerate(graphs):
+            for i, k in enumerate(("sid", "skip", "block")):
+                packed[i, b, :self.jl[b]] = g[k]
+        d = torch.from_numpy(packed).to(device)
+        self.sid, self.skip, self.block = d[0], d[1], d[2]
+        self.alt = torch.tensor([g["alt"] for g in graphs], dtype=torch.int32, device=device).reshape(-1, 2)
+        self.jlens = torch.tensor(self.jl, dtype=torch.int32, device=device)
+        self.ldg = max(self.Jmax, 1)
+
+    def index(self, n_classes, ld_j):
+        """CSR (class -> rows b * ld_j + j of the partials), utterances then states ascending: (offs, items) on the device."""
+        cls = np.concatenate([g["sid"].astype(np.int64) for g in self.graphs]) if self.graphs else np.zeros(0, np.int64)
+        rows = np.concatenate([b * ld_j + np.arange(n, dtype=np.int64) for b, n in enumerate(self.jl)]) if self.graphs \
+            else np.zeros(0, np.int64)
+        if cls.size and (cls.min() < 0 or cls.max() >= n_classes):
+            raise ValueError(f"emission class outside [0, {n_classes})")
+        order = np.argsort(cls, kind="stable")
+        offs = np.zeros(n_classes + 1, np.int64)
+        np.cumsum(np.bincount(cls, minlength=n_classes), out=offs[1:])
+        dev = self.sid.device
+        return torch.from_numpy(offs.astype(np.int32)).to(dev), torch.from_numpy(rows[order].astype(np.int32)).to(dev)
+
+
+def _check_scan(E, lens, G):
+    E = _dev(E, torch.float64, "E")
+    B, Tmax, Jmax = E.shape
+    if B != len(G.jl) or Jmax < G.Jmax:
+        raise ValueError(f"E {tuple(E.shape)} does not hold {len(G.jl)} utterances of up to {G.Jmax} states")
+    lens_h, lens_d = _lens(lens, B, Tmax, "lens", E.device)
+    return E, B, Tmax, lens_h, lens_d
+
+
+def features(mel, lens):
+    """mel (B, n_mel, frames) float32 log-mel on the device, lens frames per row -> x (B, Tmax, 2 n_mel) float64."""
+    mel = _dev(mel, torch.float32, "mel")
+    B, n_mel, F = mel.shape
+    lens_h, lens_d = _lens(lens, B, F, "lens", mel.device)
+    Tmax = max(lens_h, default=0)
+    x = torch.empty(B, Tmax, 2 * n_mel, dtype=torch.float64, device=mel.device)
+    mean = torch.empty(B, n_mel, dtype=torch.float64, device=mel.device)
+    _lib.call("fs2_align_feats", mel.data_ptr(), mel.stride(0), mel.stride(1), lens_d.data_ptr(), mean.data_ptr(), x.data_ptr(),
+              x.stride(0), x.stride(1), B, n_mel, Tmax, ops._stream())
+    return x
+
+
+def emit(x, lens, G, mu, var, out=None):
+    """E (B, Tmax, Jmax) float64 from features x (B, Tmax, D), the batch's Graphs and the class tables mu, var (C, D)."""
+    x = _dev(x, torch.float64, "x")
+    mu, var = _dev(mu, torch.float64, "mu", 2).contiguous(), _dev(var, torch.float64, "var", 2).contiguous()
+    B, Tmax, D = x.shape
+    if mu.shape != var.shape or mu.shape[1] != D or B != len(G.jl):
+        raise ValueError(f"x {tuple(x.shape)}, mu {tuple(mu.shape)}, var {tuple(var.shape)}, {len(G.jl)} graphs do not fit together")
+    _, lens_d = _lens(lens, B, Tmax, "lens", x.device)
+    E = torch.empty(B, Tmax, G.Jmax, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
+    if E.shape[0] != B or E.shape[1] < Tmax or E.shape[2] < G.Jmax:
+        raise ValueError(f"out {tuple(E.shape)} is too small for ({B}, {Tmax}, {G.Jmax})")
+    _lib.call("fs2_align_emit", x.data_ptr(), x.stride(0), x.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.sid.data_ptr(), G.ldg,
+              mu.data_ptr(), var.data_ptr(), mu.shape[0], D, E.data_ptr(), E.stride(0), E.stride(1), B, Tmax, G.Jmax, ops._stream())
+    return E
+
+
+def forward(E, lens, G, out=None):
+    """-> (alpha like E, loglik (B,)) on the device."""
+    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
+    alpha = torch.empty_like(E) if out is None else _dev(out, torch.float64, "out")
+    if alpha.shape != E.shape:
+        raise ValueError("out must have E's shape")
+    loglik = torch.empty(B, dtype=torch.float64, device=E.device)
+    _lib.call("fs2_align_forward", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.skip.data_ptr(),
+              G.ldg, G.alt.data_ptr(), alpha.data_ptr(), alpha.stride(0), alpha.stride(1), loglik.data_ptr(), B, Tmax, G.Jmax,
+              ops._stream())
+    return alpha, loglik
+
+
+def backward(E, lens, G, alpha, loglik, out=None):
+    """gamma = exp(alpha + beta - loglik), written over alpha unless `out` is given."""
+    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
+    alpha = _dev(alpha, torch.float64, "alpha")
+    gamma = alpha if out is None else _dev(out, torch.float64, "out")
+    loglik = _dev(loglik, torch.float64, "loglik", 1)
+    if alpha.shape != E.shape or gamma.shape != E.shape or loglik.shape[0] != B:
+        raise ValueError("alpha and out must have E's shape, loglik B values")
+    _lib.call("fs2_align_backward", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.skip.data_ptr(),
+              G.ldg, G.alt.data_ptr(), alpha.data_ptr(), alpha.stride(0), alpha.stride(1), loglik.data_ptr(), gamma.data_ptr(),
+              gamma.stride(0), gamma.stride(1), B, Tmax, G.Jmax, ops._stream())
+    return gamma
+
+
+def stats(gamma, x, lens, G, out=None):
+    """Per-utterance partials (B, Jmax, 1 + 2 D)."""
+    gamma, B, Tmax, _, lens_d = _check_scan(gamma, lens, G)
+    x = _dev(x, torch.float64, "x")
+    D = x.shape[2]
+    if x.shape[0] != B or x.shape[1] < Tmax:
+        raise ValueError(f"x {tuple(x.shape)} does not cover gamma {tuple(gamma.shape)}")
+    P = torch.empty(B, G.ldg, 1 + 2 * D, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
+    if P.shape[0] != B or P.shape[1] < G.Jmax or P.shape[2] != 1 + 2 * D:
+        raise ValueError(f"out {tuple(P.shape)} is not ({B}, >= {G.Jmax}, {1 + 2 * D})")
+    _lib.call("fs2_align_stats", gamma.data_ptr(), gamma.stride(0), gamma.stride(1), x.data_ptr(), x.stride(0), x.stride(1),
+              lens_d.data_ptr(), G.jlens.data_ptr(), D, P.data_ptr(), P.stride(0), P.stride(1), B, Tmax, G.Jmax, ops._stream())
+    return P
+
+
+def reduce(P, G, n_classes, sums=None, index=None):
+    """Class sums (C, 1 + 2 D) of the partials; added to `sums` when given."""
+    P = _dev(P, torch.float64, "partials")
+    if not P.is_contiguous():
+        raise ValueError("partials must be contiguous")
+    offs, items = index if index is not None else G.index(n_classes, P.shape[1])
+    acc = sums is not None
+    if sums is None:
+        sums = torch.empty(n_classes, P.shape[2], dtype=torch.float64, device=P.device)
+    _lib.call("fs2_align_reduce", P.data_ptr(), P.stride(1), P.shape[0] * P.shape[1], offs.data_ptr(), items.data_ptr(), n_classes,
+              P.shape[2], sums.data_ptr(), int(acc), ops._stream())
+    return sums
+
+
+def viterbi(E, lens, G, out=None):
+    """-> (backpointers uint8 like E, best end state (B,) int32, its score (B,) float64)."""
+    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
+    bp = torch.empty(E.shape, dtype=torch.uint8, device=E.device) if out is None else _dev(out, torch.uint8, "out")
+    if bp.shape != E.shape:
+        raise ValueError("out must have E's shape")
+    end = torch.empty(B, dtype=torch.int32, device=E.device)
+    score = torch.empty(B, dtype=torch.float64, device=E.device)
+    _lib.call("fs2_align_viterbi", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.skip.data_ptr(),
+              G.ldg, G.alt.data_ptr(), bp.data_ptr(), bp.stride(0), bp.stride(1), end.data_ptr(), score.data_ptr(), B, Tmax, G.Jmax,
+              ops._stream())
+    return bp, end, score
+
+
+def backtrack(bp, lens, G, end):
+    """-> frames per block (B, nbmax) int32 on the device."""
+    bp = _dev(bp, torch.uint8, "bp")
+    B, Tmax, Jmax = bp.shape
+    if B != len(G.jl) or Jmax < G.Jmax:
+        raise ValueError(f"bp {tuple(bp.shape)} does not hold {len(G.jl)} utterances of up to {G.Jmax} states")
+    _, lens_d = _lens(lens, B, Tmax, "lens", bp.device)
+    end = _dev(end, torch.int32, "end", 1)
+    frames = torch.empty(B, max(G.nbmax, 1), dtype=torch.int32, device=bp.device)
+    _lib.call("fs2_align_backtrack", bp.data_ptr(), bp.stride(0), bp.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.skip.data_ptr(), G.block.data_ptr(), G.ldg, end.data_ptr(), frames.data_ptr(), frames.shape[1], B, Tmax, G.Jmax,
+              ops._stream())
+    return frames
+
+
+# ------------------------------------------------------------------------------------------------ the model
+class Aligner:
+    """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`."""
+
+    def __init__(self, n_classes, dim, states=2, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("fastspeech2_amd.align runs on an AMD GPU only (no CPU fallback): pass device='cuda'")
+        if n_classes % states:
+            raise ValueError(f"n_classes {n_classes} is not a multiple of states {states}")
+        self.n_classes, self.dim, self.states = n_classes, dim, states
+        self.mu = torch.zeros(n_classes, dim, dtype=torch.float64, device=self.device)
+        self.var = torch.ones(n_classes, dim, dtype=torch.float64, device=self.device)
+        self.floor = np.zeros(dim)
+
+    def _prepare(self, feats, lens, graphs):
+        lens = [int(v) for v in lens]
+        if len(lens) != len(graphs) or len(lens) != feats.shape[0]:
+            raise ValueError(f"{feats.shape[0]} feature rows, {len(lens)} lengths and {len(graphs)} graphs")
+        if feats.dim() != 3 or feats.shape[2] != self.dim or feats.dtype != torch.float64:
+            raise ValueError(f"feats must be (B, Tmax, {self.dim}) float64, got {feats.dtype} {tuple(feats.shape)}")
+        for n, g in zip(lens, graphs):
+            if n < g["mandatory"] or n > feats.shape[1]:
+                raise ValueError(f"an utterance of {n} frames cannot pass its {g['mandatory']} mandatory states "
+                                 f"(or exceeds the {feats.shape[1]} rows of feats)")
+        G = Graphs(graphs, self.device)
+        return lens, G
+
+    def _set(self, mu, var):
+        self.mu.copy_(torch.from_numpy(np.ascontiguousarray(mu)))
+        self.var.copy_(torch.from_numpy(np.ascontiguousarray(var)))
+
+    def fit(self, batches, iters=12):
+        """batches: [(feats (B, Tmax, D) float64 on the device or the host, lens, graphs)].  Flat start, then `iters` Baum-Welch
+        passes; returns the log-likelihood per frame of every pass."""
+        prep = []
+        for feats, lens, graphs in batches:
+            lens, G = self._prepare(feats, lens, graphs)
+            prep.append((feats, lens, G, G.index(self.n_classes, G.ldg)))
+        n_frames = sum(sum(lens) for _, lens, _, _ in prep)
+        cols = 1 + 2 * self.dim
+
+        # flat start: the hard assignment as a one-hot gamma through the same statistics kernels
+        sums = None
+        for feats, lens, G, index in prep:
+            x = feats.to(self.device, non_blocking=True)
+            B, Tmax = x.shape[0], x.shape[1]
+            assign = np.zeros((B, Tmax), np.int64)
+            for b, g in enumerate(G.graphs):
+                assign[b, :lens[b]] = flat_assignment(g, lens[b])
+            gamma = torch.zeros(B, Tmax, G.ldg, dtype=torch.float64, device=self.device)
+            gamma.scatter_(2, torch.from_numpy(assign).to(self.device).unsqueeze(2), 1.0)
+            sums = reduce(stats(gamma, x, lens, G), G, self.n_classes, sums, index)
+            del gamma
+        if sums is None:
+            raise ValueError("no utterances to train on")
+        s = sums.cpu().numpy()
+        tot = s.sum(axis=0)
+        g_mean = tot[1:1 + self.dim] / tot[0]
+        g_var = tot[1 + self.dim:] / tot[0] - g_mean * g_mean
+        self.floor = VAR_FLOOR * g_var
+        mu, var = m_step(s, np.tile(g_mean, (self.n_classes, 1)), np.tile(g_var, (self.n_classes, 1)), self.floor)
+        self._set(mu, var)
+
+        history = []
+        for _ in range(iters):
+            sums, total = None, 0.0
+            for feats, lens, G, index in prep:
+                x = feats.to(self.device, non_blocking=True)
+                E = emit(x, lens, G, self.mu, self.var)
+                alpha, loglik = forward(E, lens, G)
+                gamma = backward(E, lens, G, alpha, loglik)
+                sums = reduce(stats(gamma, x, lens, G), G, self.n_classes, sums, index)
+                total += float(np.sum(loglik.cpu().numpy()))
+                del E, alpha, gamma
+            mu, var = m_step(sums.cpu().numpy(), mu, var, self.floor)
+            self._set(mu, var)
+            history.append(total / n_frames)
+        return history
+
+    def align(self, feats, lens, graphs):
+        """Viterbi alignment of one ragged batch -> [frames per block (int32 numpy)] per utterance."""
+        lens, G = self._prepare(feats, lens, graphs)
+        x = feats.to(self.device, non_blocking=True)
+        E = emit(x, lens, G, self.mu, self.var)
+        bp, end, _ = viterbi(E, lens, G)
+        frames = backtrack(bp, lens, G, end).cpu().numpy()
+        return [frames[b, :len(g["blocks"])].copy() for b, g in enumerate(graphs)]
+
+
+# ------------------------------------------------------------------------------------------------ the corpus pass
+def batches_by_bytes(frames, states, dim, budget):
+    """Longest first, then greedy packing of PADDED batches under `budget` bytes of device buffers (E, alpha / gamma, backpointers,
+    features, partials), as `Preprocessor._batches` packs audio."""
+    order = sorted(range(len(frames)), key=lambda i: (-frames[i], -states[i], i))
+    cost = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
+    batch, T, J = [], 0, 0
+    for i in order:
+        if batch and cost(len(batch) + 1, max(T, frames[i]), max(J, states[i])) > budget:
+            yield batch
+            batch, T, J = [], 0, 0
+        batch.append(i)
+        T, J = max(T, frames[i]), max(J, states[i])
+    if batch:
+        yield batch
+
+
+def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
+          batch_seconds=1800.0, num_workers=8):
+    """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
+    log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
+    from . import audio as Audio
+    from .preprocess import load_wav
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("fastspeech2_amd.align runs on an AMD GPU only (no CPU fallback): pass device='cuda'")
+    raw, out_dir = config["path"]["raw_path"], os.path.join(config["path"]["preprocessed_path"], "TextGrid")
+    pp = config["preprocessing"]
+    sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
+    lexicon = read_lexicon(config["path"]["lexicon_path"])
+    phone_ids = phone_table(lexicon)
+    stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], n_mel, sr, pp["mel"]["mel_fmin"],
+                              pp["mel"]["mel_fmax"])
+
+    entries = []
+    for speaker in sorted(os.listdir(raw)):
+        if not os.path.isdir(os.path.join(raw, speaker)):
+            continue
+        for name in sorted(os.listdir(os.path.join(raw, speaker))):
+            if name.endswith(".wav") and os.path.exists(os.path.join(raw, speaker, name[:-4] + ".lab")):
+                entries.append((speaker, name[:-4]))
+    tg = lambda e: os.path.join(out_dir, e[0], e[1] + ".TextGrid")                       # noqa: E731
+    existing = [e for e in entries if os.path.exists(tg(e))]
+    if existing and not overwrite:
+        raise FileExistsError(f"{len(existing)} TextGrids exist already (first: {tg(existing[0])}); pass --overwrite to replace them")
+
+    def read(e):
+        wav = np.clip(load_wav(os.path.join(raw, e[0], e[1] + ".wav"), sr), -1.0, 1.0).astype(np.float32)
+        with open(os.path.join(raw, e[0], e[1] + ".lab"), encoding="utf-8") as f:
+            return wav, words_of(f.readline())
+
+    # stage 1: wav + lab on a host thread pool, log-mel + features on the GPU per ragged batch of audio, features back to the host
+    items, skipped = [], []
+    batch_samples = int(batch_seconds * sr)
+
+    def extract(chunk):
+        order = sorted(range(len(chunk)), key=lambda i: -len(chunk[i][1]))
+        batch = []
+        for i in order + [None]:
+            if batch and (i is None or (len(batch) + 1) * len(chunk[batch[0]][1]) > batch_samples):
+                lens = [len(chunk[k][1]) for k in batch]
+                host = torch.zeros(len(batch), max(lens), dtype=torch.float32)
+                for r, k in enumerate(batch):
+                    host[r, :lens[r]] = torch.from_numpy(chunk[k][1])
+                mel, _, fr = stft.mel_spectrogram_ragged(host.to(dev), torch.tensor(lens, dtype=torch.int32))
+                x = features(mel.contiguous(), fr.tolist()).cpu()
+                for r, k in enumerate(batch):
+                    e, _, words, graph = chunk[k]
+                    items.append({"entry": e, "words": words, "graph": graph, "x": x[r, :int(fr[r])].clone()})
+                batch = []
+            if i is not None:
+                batch.append(i)
+
+    with ThreadPoolExecutor(max_workers=max(1, num_workers)) as pool:
+        step = max(64, 8 * num_workers)
+        for c0 in range(0, len(entries), step):
+            chunk = []
+            for e, (wav, words) in zip(entries[c0:c0 + step], pool.map(read, entries[c0:c0 + step])):
+                if not words:
+                    skipped.append((e[0], e[1], "empty transcript"))
+                    continue
+                graph = utterance_graph(words, lexicon, phone_ids, states)
+                T = len(wav) // hop + 1
+                if len(wav) <= pp["stft"]["filter_length"] // 2 or T < graph["mandatory"]:
+                    skipped.append((e[0], e[1], f"{T} frames for {graph['mandatory']} mandatory states"))
+                elif len(graph["sid"]) > max_states():
+                    skipped.append((e[0], e[1], f"{len(graph['sid'])} states exceed the supported {max_states()}"))
+                else:
+                    chunk.append((e, wav, words, graph))
+            if chunk:
+                extract(chunk)
+    for s in skipped:
+        print("skipped {}/{}: {}".format(*s))
+    if not items:
+        return 0, skipped, []
+
+    # stage 2: ragged batches under the byte budget; the packed features stay on the device when the corpus fits
+    D = 2 * n_mel
+    frames, nstates = [it["x"].shape[0] for it in items], [len(it["graph"]["sid"]) for it in items]
+    resident = sum(frames) * D * 8 <= resident_bytes
+    packed = []
+    for batch in batches_by_bytes(frames, nstates, D, batch_bytes):
+        feats = torch.zeros(len(batch), max(frames[i] for i in batch), D, dtype=torch.float64)
+        for r, i in enumerate(batch):
+            feats[r, :frames[i]] = items[i]["x"]
+            items[i]["x"] = None
+        packed.append((feats.to(dev) if resident else feats, [frames[i] for i in batch], [items[i]["graph"] for i in batch], batch))
+    aligner = Aligner(len(phone_ids) * states, D, states, dev)
+    history = aligner.fit([p[:3] for p in packed], iters)
+
+    written = 0
+    for feats, lens, graphs, batch in packed:
+        for i, fr in zip(batch, aligner.align(feats, lens, graphs)):
+            e = items[i]["entry"]
+            os.makedirs(os.path.join(out_dir, e[0]), exist_ok=True)
+            wd, ph, xmax = intervals(items[i]["graph"], items[i]["words"], fr, hop, sr)
+            write_textgrid(tg(e), wd, ph, xmax)
+            written += 1
+    return written, skipped, history

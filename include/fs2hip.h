@@ -366,6 +366,46 @@ int fs2_f0_fix(const double* cand, const double* score, const int32_t* frames, i
 int fs2_f0_stonemask(const float* x, long ldx, const int32_t* lens, const double* f0, const int32_t* frames, double fs,
                      double frame_period, double* out, int B, int Fmax, int Nmax, fs2_stream_t stream);
 
+/* ---- forced alignment: monophone HMM, Baum-Welch + Viterbi (specification: fastspeech2_amd/align.py) ----
+ * fp64 throughout, ragged batches: utterance b has lens[b] frames and jlens[b] states (both int32, device); buffers are
+ * [B][Tmax][Jmax] with explicit batch / frame strides in elements, graph rows sid / skip / block are [B][Jmax] int32 with row stride
+ * ldg.  Nothing at t >= lens[b] or j >= jlens[b] is read or written.  alt[b] = {alternative start state or -1, alternative end state
+ * or -1}: a path starts in state 0 or alt[b][0] and ends in state jlens[b] - 1 or alt[b][1].  No atomics: results do not depend on
+ * the rest of the batch or on the run.  Jmax above fs2_align_max_states() is FS2_EINVAL. */
+int fs2_align_max_states(void);
+/* log-mel [B][n_mel][frames] f32 (strides ldm_b, ldm_c) -> x [B][Tmax][2 n_mel]: per-utterance mean removed, then the central
+ * differences (x[t+1] - x[t-1]) / 2 with edge replication appended; mean [B][n_mel] is workspace */
+int fs2_align_feats(const float* mel, long ldm_b, long ldm_c, const int32_t* lens, double* mean, double* x, long ldx_b, long ldx_t,
+                    int B, int n_mel, int Tmax, fs2_stream_t stream);
+/* E[b][t][j] = -1/2 sum_d ((x_d - mu_d)^2 / var_d + log(2 pi var_d)) for class sid[b][j] of the [n_classes][D] tables mu, var */
+int fs2_align_emit(const double* x, long ldx_b, long ldx_t, const int32_t* lens, const int32_t* jlens, const int32_t* sid, long ldg,
+                   const double* mu, const double* var, int n_classes, int D, double* E, long lde_b, long lde_t, int B, int Tmax,
+                   int Jmax, fs2_stream_t stream);
+/* log-domain forward recursion over the arcs self, next (j - 1) and skip[b][j] -> alpha, loglik[b] over the end states */
+int fs2_align_forward(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                      long ldg, const int32_t* alt, double* alpha, long lda_b, long lda_t, double* loglik, int B, int Tmax, int Jmax,
+                      fs2_stream_t stream);
+/* backward recursion (beta stays on the chip) -> gamma = exp(alpha + beta - loglik); gamma may be alpha itself (equal strides) */
+int fs2_align_backward(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                       long ldg, const int32_t* alt, const double* alpha, long lda_b, long lda_t, const double* loglik, double* gamma,
+                       long ldo_b, long ldo_t, int B, int Tmax, int Jmax, fs2_stream_t stream);
+/* partials[b][j] = sum_t gamma[b][t][j] * {1, x[b][t][0..D), x[b][t][0..D)^2} (1 + 2 D columns, strides ldp_b, ldp_j), ascending t */
+int fs2_align_stats(const double* gamma, long ldo_b, long ldo_t, const double* x, long ldx_b, long ldx_t, const int32_t* lens,
+                    const int32_t* jlens, int D, double* partials, long ldp_b, long ldp_j, int B, int Tmax, int Jmax,
+                    fs2_stream_t stream);
+/* sums[c][0..cols) = (accumulate ? sums[c] : 0) + the rows items[offs[c] .. offs[c + 1]) of partials (as [n_rows][ldp_j]), in list order */
+int fs2_align_reduce(const double* partials, long ldp_j, long n_rows, const int32_t* offs, const int32_t* items, int n_classes,
+                     int cols, double* sums, int accumulate, fs2_stream_t stream);
+/* Viterbi: bp[b][t][j] = 0 self / 1 next / 2 skip (lowest code on ties, row 0 is 0), end[b] = best end state (lower index on ties),
+ * score[b] its log-probability */
+int fs2_align_viterbi(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                      long ldg, const int32_t* alt, uint8_t* bp, long ldp_b, long ldp_t, int32_t* end, double* score, int B, int Tmax,
+                      int Jmax, fs2_stream_t stream);
+/* frames[b][k] = frames the best path spends in block k (block[b][j] = block of state j), zero-filled up to nbmax */
+int fs2_align_backtrack(const uint8_t* bp, long ldp_b, long ldp_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                        const int32_t* block, long ldg, const int32_t* end, int32_t* frames, int nbmax, int B, int Tmax, int Jmax,
+                        fs2_stream_t stream);
+
 /* ---- loss (model/loss.py:19-92): masked L1 (mel, post-net mel) + masked MSE (pitch, energy, log-duration) ----
  * mel / post: [B][T][n_mel] f32 predictions; mel_t: target with batch stride ld_t_b (its own padded length >= T);
  * lens int64 (valid = t < min(len, T)); p/e predictions [B][L] (phoneme level) or [B][T] (p_frame / e_frame = 1) with
