@@ -53,7 +53,7 @@ from string import punctuation
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ragged
 
 SIL, SP, SPN = "sil", "sp", "spn"
 VAR_FLOOR = 1e-2
@@ -169,18 +169,10 @@ def max_states():
 
 
 def _dev(t, dtype, what, dim=3):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("fastspeech2_amd.align runs on an AMD GPU only (no CPU fallback): pass device tensors")
+    ragged.require_device(t, "fastspeech2_amd.align")
     if t.dtype != dtype or t.dim() != dim or (t.numel() and t.stride(-1) != 1):
         raise ValueError(f"{what} must be a {dim}-D {dtype} tensor with unit inner stride, got {t.dtype} {tuple(t.shape)}")
     return t
-
-
-def _lens(lens, B, cap, what, dev):
-    h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-    if len(h) != B or any(n < 0 or n > cap for n in h):
-        raise ValueError(f"{what} must hold B={B} lengths in [0, {cap}], got {h}")
-    return h, torch.tensor(h, dtype=torch.int32, device=dev)
 
 
 class Graphs:
@@ -222,7 +214,7 @@ def _check_scan(E, lens, G):
     B, Tmax, Jmax = E.shape
     if B != len(G.jl) or Jmax < G.Jmax:
         raise ValueError(f"E {tuple(E.shape)} does not hold {len(G.jl)} utterances of up to {G.Jmax} states")
-    lens_h, lens_d = _lens(lens, B, Tmax, "lens", E.device)
+    lens_h, lens_d = ragged.lengths(lens, B, Tmax, "lens", E.device)
     return E, B, Tmax, lens_h, lens_d
 
 
@@ -230,7 +222,7 @@ def features(mel, lens):
     """mel (B, n_mel, frames) float32 log-mel on the device, lens frames per row -> x (B, Tmax, 2 n_mel) float64."""
     mel = _dev(mel, torch.float32, "mel")
     B, n_mel, F = mel.shape
-    lens_h, lens_d = _lens(lens, B, F, "lens", mel.device)
+    lens_h, lens_d = ragged.lengths(lens, B, F, "lens", mel.device)
     Tmax = max(lens_h, default=0)
     x = torch.empty(B, Tmax, 2 * n_mel, dtype=torch.float64, device=mel.device)
     mean = torch.empty(B, n_mel, dtype=torch.float64, device=mel.device)
@@ -246,7 +238,7 @@ def emit(x, lens, G, mu, var, out=None):
     B, Tmax, D = x.shape
     if mu.shape != var.shape or mu.shape[1] != D or B != len(G.jl):
         raise ValueError(f"x {tuple(x.shape)}, mu {tuple(mu.shape)}, var {tuple(var.shape)}, {len(G.jl)} graphs do not fit together")
-    _, lens_d = _lens(lens, B, Tmax, "lens", x.device)
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", x.device)
     E = torch.empty(B, Tmax, G.Jmax, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
     if E.shape[0] != B or E.shape[1] < Tmax or E.shape[2] < G.Jmax:
         raise ValueError(f"out {tuple(E.shape)} is too small for ({B}, {Tmax}, {G.Jmax})")
@@ -331,7 +323,7 @@ def backtrack(bp, lens, G, end):
     B, Tmax, Jmax = bp.shape
     if B != len(G.jl) or Jmax < G.Jmax:
         raise ValueError(f"bp {tuple(bp.shape)} does not hold {len(G.jl)} utterances of up to {G.Jmax} states")
-    _, lens_d = _lens(lens, B, Tmax, "lens", bp.device)
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", bp.device)
     end = _dev(end, torch.int32, "end", 1)
     frames = torch.empty(B, max(G.nbmax, 1), dtype=torch.int32, device=bp.device)
     _lib.call("fs2_align_backtrack", bp.data_ptr(), bp.stride(0), bp.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
@@ -345,9 +337,7 @@ class Aligner:
     """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`."""
 
     def __init__(self, n_classes, dim, states=2, device="cuda"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("fastspeech2_amd.align runs on an AMD GPU only (no CPU fallback): pass device='cuda'")
+        self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
         if n_classes % states:
             raise ValueError(f"n_classes {n_classes} is not a multiple of states {states}")
         self.n_classes, self.dim, self.states = n_classes, dim, states
@@ -432,19 +422,10 @@ class Aligner:
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
 def batches_by_bytes(frames, states, dim, budget):
-    """Longest first, then greedy packing of PADDED batches under `budget` bytes of device buffers (E, alpha / gamma, backpointers,
-    features, partials), as `Preprocessor._batches` packs audio."""
-    order = sorted(range(len(frames)), key=lambda i: (-frames[i], -states[i], i))
+    """`ragged.greedy_batches` of (frames, states) under `budget` bytes of device buffers: E, alpha / gamma and backpointers (17 B per
+    cell), features, partials."""
     cost = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
-    batch, T, J = [], 0, 0
-    for i in order:
-        if batch and cost(len(batch) + 1, max(T, frames[i]), max(J, states[i])) > budget:
-            yield batch
-            batch, T, J = [], 0, 0
-        batch.append(i)
-        T, J = max(T, frames[i]), max(J, states[i])
-    if batch:
-        yield batch
+    return ragged.greedy_batches(list(zip(frames, states)), budget, cost)
 
 
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
@@ -453,9 +434,7 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
     from . import audio as Audio
     from .preprocess import load_wav
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("fastspeech2_amd.align runs on an AMD GPU only (no CPU fallback): pass device='cuda'")
+    dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
     raw, out_dir = config["path"]["raw_path"], os.path.join(config["path"]["preprocessed_path"], "TextGrid")
     pp = config["preprocessing"]
     sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
@@ -485,23 +464,17 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     items, skipped = [], []
     batch_samples = int(batch_seconds * sr)
 
+    staging = ragged.Staging()
+
     def extract(chunk):
-        order = sorted(range(len(chunk)), key=lambda i: -len(chunk[i][1]))
-        batch = []
-        for i in order + [None]:
-            if batch and (i is None or (len(batch) + 1) * len(chunk[batch[0]][1]) > batch_samples):
-                lens = [len(chunk[k][1]) for k in batch]
-                host = torch.zeros(len(batch), max(lens), dtype=torch.float32)
-                for r, k in enumerate(batch):
-                    host[r, :lens[r]] = torch.from_numpy(chunk[k][1])
-                mel, _, fr = stft.mel_spectrogram_ragged(host.to(dev), torch.tensor(lens, dtype=torch.int32))
-                x = features(mel.contiguous(), fr.tolist()).cpu()
-                for r, k in enumerate(batch):
-                    e, _, words, graph = chunk[k]
-                    items.append({"entry": e, "words": words, "graph": graph, "x": x[r, :int(fr[r])].clone()})
-                batch = []
-            if i is not None:
-                batch.append(i)
+        for batch in ragged.greedy_batches([(len(c[1]),) for c in chunk], batch_samples, ragged.padded_samples):
+            wavs = [chunk[k][1] for k in batch]
+            staging.pack(wavs)
+            mel, _, fr = stft.mel_spectrogram_ragged(staging.to(dev), [len(w) for w in wavs])
+            x = features(mel.contiguous(), fr.tolist()).cpu()
+            for r, k in enumerate(batch):
+                e, _, words, graph = chunk[k]
+                items.append({"entry": e, "words": words, "graph": graph, "x": x[r, :int(fr[r])].clone()})
 
     with ThreadPoolExecutor(max_workers=max(1, num_workers)) as pool:
         step = max(64, 8 * num_workers)

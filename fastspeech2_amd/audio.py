@@ -29,7 +29,7 @@ import functools
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ragged
 from .resample import peak_abs, peaknorm_pcm, resample_poly  # noqa: F401
 
 
@@ -129,11 +129,6 @@ def _framed_dft(forward_basis, y, B, N, lens, filter_length, hop):
     return ft, S
 
 
-def _require_cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"fastspeech2_amd.audio.{what} runs on an AMD GPU only (no CPU fallback)")
-
-
 class STFT(torch.nn.Module):
     """audio/stft.py:15-127 on the GPU: `transform(x (B, N))` -> (magnitude, phase), each (B, cutoff, 1 + N // hop);
     `inverse(magnitude, phase)` -> (B, 1, hop * (F - 1)); `forward(x)` = inverse(*transform(x)).  fp32 throughout: the framed
@@ -164,7 +159,7 @@ class STFT(torch.nn.Module):
 
     def transform(self, input_data):
         """stft.py:52-81 -> (magnitude, phase), each (B, cutoff, 1 + N // hop); needs N > filter_length / 2 (reflect pad)."""
-        _require_cuda(input_data, "STFT")
+        ragged.require_device(input_data, "fastspeech2_amd.audio.STFT")
         self._to(input_data.device)
         x = input_data.contiguous().float()
         B, N = x.shape
@@ -179,7 +174,7 @@ class STFT(torch.nn.Module):
 
     def inverse(self, magnitude, phase):
         """stft.py:83-122: (B, cutoff, F) magnitude and phase -> (B, 1, hop * (F - 1))."""
-        _require_cuda(magnitude, "STFT")
+        ragged.require_device(magnitude, "fastspeech2_amd.audio.STFT")
         self._to(magnitude.device)
         magnitude = magnitude.float()
         phase = torch.as_tensor(phase, dtype=torch.float32, device=magnitude.device)
@@ -263,7 +258,7 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None):
     if NF != stft_fn.cutoff:
         raise ValueError(f"griffin_lim: magnitudes {tuple(magnitudes.shape)}: need (B, {stft_fn.cutoff}, F)")
     _check_frames([F], stft_fn.hop_length, stft_fn.filter_length)
-    _require_cuda(magnitudes, "griffin_lim")
+    ragged.require_device(magnitudes, "fastspeech2_amd.audio.griffin_lim")
     stft_fn._to(magnitudes.device)
     mag = magnitudes.float()
     if angles is None:
@@ -282,13 +277,13 @@ def mels_to_wavs_griffin_lim(mels, mel_lens, _stft, n_iters=60, angles=None, ws=
     generator; every utterance's result is bit-identical to the utterance processed alone.  angles (optional): list of B
     (cutoff, mel_lens[b] - 1) arrays.  ws (optional): a workspace(B, max(mel_lens) - 1, device) to run in."""
     stft = _stft.stft_fn
-    lens = [int(x) for x in (mel_lens.tolist() if isinstance(mel_lens, torch.Tensor) else mel_lens)]
     B, n_mel, T = mels.shape
+    if n_mel != _stft.n_mel_channels:
+        raise ValueError(f"mels_to_wavs_griffin_lim: mels {tuple(mels.shape)}: need (B, {_stft.n_mel_channels}, T)")
+    lens, lens_d = ragged.lengths(mel_lens, B, T, "mel_lens", mels.device)
     frames = [n - 1 for n in lens]
     _check_frames(frames, stft.hop_length, stft.filter_length)
-    if len(lens) != B or max(lens) > T or n_mel != _stft.n_mel_channels:
-        raise ValueError(f"mels_to_wavs_griffin_lim: mels {tuple(mels.shape)}, mel_lens {lens}")
-    _require_cuda(mels, "mels_to_wavs_griffin_lim")
+    ragged.require_device(mels, "fastspeech2_amd.audio.mels_to_wavs_griffin_lim")
     _stft._to(mels.device)
     mels = mels.float()
     dev, NF, Fmax = mels.device, stft.cutoff, max(frames)
@@ -298,7 +293,6 @@ def mels_to_wavs_griffin_lim(mels, mel_lens, _stft, n_iters=60, angles=None, ws=
     for b, (a, f) in enumerate(zip(angles, frames)):
         host[b, :, :f] = np.asarray(a, dtype=np.float32).reshape(NF, f)
     ang = torch.from_numpy(host).to(dev)
-    lens_d = torch.tensor(lens, dtype=torch.int32).to(dev)
     frames_d = lens_d - 1
     mag = torch.empty(B, Fmax, NF, device=dev, dtype=torch.float32)                    # frame-major target magnitude
     _lib.call("fs2_gl_mel_to_mag", mels.data_ptr(), mels.stride(0), mels.stride(1), mels.stride(2), lens_d.data_ptr(),
@@ -362,16 +356,14 @@ class TacotronSTFT(torch.nn.Module):
 
     def spectral_de_normalize(self, magnitudes):
         """stft.py:155-157 (audio_processing.py:94-100, C = 1): exp(x)."""
-        _require_cuda(magnitudes, "TacotronSTFT")
+        ragged.require_device(magnitudes, "fastspeech2_amd.audio.TacotronSTFT")
         return torch.exp(magnitudes)
 
     def mel_spectrogram(self, y):
         """audio/stft.py:159-178."""
         assert torch.min(y.data) >= -1 and torch.max(y.data) <= 1          # stft.py:170-171
-        if not y.is_cuda:
-            raise RuntimeError("fastspeech2_amd.audio.TacotronSTFT runs on an AMD GPU only (no CPU fallback)")
-        if self.forward_basis.device != y.device:
-            self.to(y.device)
+        ragged.require_device(y, "fastspeech2_amd.audio.TacotronSTFT")
+        self._to(y.device)
         y = y.contiguous().float()
         B, N = y.shape
         return self._framed_mel(y, B, N, None)
@@ -381,15 +373,12 @@ class TacotronSTFT(torch.nn.Module):
         B utterances of `lens[b]` samples each (anything beyond is ignored).  Every row is reflected at its OWN end, so
         frames [0, lens[b] // hop + 1) of row b are bit-identical to the utterance processed alone; later frames are padding.
         Returns (mel (B, n_mel, Nmax // hop + 1), energy (B, Nmax // hop + 1), frames (B,) int64)."""
-        if not y.is_cuda:
-            raise RuntimeError("fastspeech2_amd.audio.TacotronSTFT runs on an AMD GPU only (no CPU fallback)")
-        if self.forward_basis.device != y.device:
-            self.to(y.device)
+        ragged.require_device(y, "fastspeech2_amd.audio.TacotronSTFT")
+        self._to(y.device)
         y = y.contiguous().float()
         B, N = y.shape
-        lens = torch.as_tensor(lens, device=y.device).to(torch.int32).contiguous()
-        assert lens.numel() == B and int(lens.max()) <= N and int(lens.min()) > self.filter_length // 2, \
-            "each utterance needs more than filter_length/2 samples (reflect padding) and must fit its row"
+        lens_h, lens = ragged.lengths(lens, B, N, "lens", y.device)
+        assert lens_h and min(lens_h) > self.filter_length // 2, "each utterance needs more than filter_length/2 samples (reflect padding)"
         mel, energy = self._framed_mel(y, B, N, lens)
         return mel, energy, lens.to(torch.int64) // self.hop_length + 1
 

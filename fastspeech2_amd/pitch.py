@@ -55,7 +55,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ragged
 
 F0_FLOOR, F0_CEIL, CHANNELS_IN_OCTAVE, ALLOWED_RANGE = 71.0, 800.0, 2.0, 0.1
 
@@ -112,20 +112,6 @@ def _device_consts(dev, fs, f0_floor, f0_ceil, channels_in_octave):
     return _consts[key]
 
 
-def _check(y, lens):
-    if not isinstance(y, torch.Tensor) or not y.is_cuda:
-        raise RuntimeError("fastspeech2_amd.pitch runs on an AMD GPU only (no CPU fallback): pass a device tensor")
-    if y.dim() != 2:
-        raise ValueError(f"y must be (B, N), got shape {tuple(y.shape)}")
-    if y.dtype != torch.float32:
-        raise ValueError(f"y must be float32, got {y.dtype}")
-    y = y.contiguous()
-    lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-    if len(lens_h) != y.shape[0] or any(n < 0 or n > y.shape[1] for n in lens_h):
-        raise ValueError(f"lens must hold B={y.shape[0]} lengths in [0, {y.shape[1]}], got {lens_h}")
-    return y, lens_h, torch.tensor(lens_h, dtype=torch.int32, device=y.device)
-
-
 def _frames(lens_h, fs, frame_period, dev):
     frames_h = [frame_count(n, fs, frame_period) for n in lens_h]
     Fmax = max(frames_h) if frames_h else 0
@@ -136,7 +122,7 @@ def dio(y, lens, fs, frame_period, f0_floor=F0_FLOOR, f0_ceil=F0_CEIL, channels_
         allowed_range=ALLOWED_RANGE):
     """DIO over a ragged batch: y (B, N) float32 on the GPU, row b holds lens[b] samples.  Returns (f0 (B, Fmax) float64 on the
     device, t (Fmax,) float64, frames (B,) int64); f0[b, frames[b]:] = 0."""
-    y, lens_h, lens_d = _check(y, lens)
+    y, lens_h, lens_d = ragged.rows(y, lens, "fastspeech2_amd.pitch")
     dev, (B, N) = y.device, y.shape
     c = _device_consts(dev, fs, f0_floor, f0_ceil, channels_in_octave)
     frames_h, Fmax, frames_d = _frames(lens_h, fs, frame_period, dev)
@@ -174,17 +160,14 @@ def dio(y, lens, fs, frame_period, f0_floor=F0_FLOOR, f0_ceil=F0_CEIL, channels_
 def stonemask(y, lens, f0, frames, fs, frame_period):
     """StoneMask refinement of `f0` (B, Fmax) float64 (device) from the rows of y (B, N) float32 (device); frames (B,) as dio
     returns.  Returns a new (B, Fmax) float64 device tensor."""
-    y, lens_h, lens_d = _check(y, lens)
+    y, lens_h, lens_d = ragged.rows(y, lens, "fastspeech2_amd.pitch")
     if not isinstance(f0, torch.Tensor) or f0.device != y.device or f0.dtype != torch.float64 or f0.dim() != 2 \
             or f0.shape[0] != y.shape[0]:
         raise ValueError("f0 must be a (B, Fmax) float64 tensor on y's device")
-    frames_h = [int(v) for v in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
-    if len(frames_h) != y.shape[0] or any(n < 0 or n > f0.shape[1] for n in frames_h):
-        raise ValueError(f"frames must hold B={y.shape[0]} counts in [0, {f0.shape[1]}]")
+    _, frames_d = ragged.lengths(frames, y.shape[0], f0.shape[1], "frames", y.device)
     f0 = f0.contiguous()
     B, Fmax = f0.shape
     out = torch.empty_like(f0)
-    frames_d = torch.tensor(frames_h, dtype=torch.int32, device=y.device)
     _lib.call("fs2_f0_stonemask", y.data_ptr(), y.shape[1], lens_d.data_ptr(), f0.data_ptr(), frames_d.data_ptr(), float(fs),
               float(frame_period), out.data_ptr(), B, Fmax, y.shape[1], ops._stream())
     return out

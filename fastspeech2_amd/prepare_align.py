@@ -16,8 +16,8 @@ Text goes through `text._clean` (its `english_cleaners` warning says what is not
 
 Audio.  The reference resamples one file at a time on the host (`librosa.load(path, sampling_rate)`) and then writes
 `(wav / max|wav| * max_wav_value).astype(int16)`.  Here a host thread pool reads files as mono float32 at their own rate
-(`preprocess.load_wav(resample=False)`); utterances are grouped by source rate and packed, longest first, into ragged batches of up
-to `batch_seconds` of padded audio; per batch: one H2D copy -> `resample.resample_poly` -> `peak_abs` -> `peaknorm_pcm` -> one
+(`preprocess.load_wav(resample=False)`); utterances are grouped by source rate and packed into ragged batches of up to
+`batch_seconds` of padded audio (`ragged.keyed_batches`); per batch: `ragged.Staging` -> one H2D copy -> `resample.resample_poly` -> `peak_abs` -> `peaknorm_pcm` -> one
 D2H copy of the int16 rows -> `scipy.io.wavfile.write`.  A file already at the target rate skips the resampler and is still
 normalised, as the reference does to LJSpeech.  The filter, the cast (a positive peak sample times 32768 wraps to -32768, as in the
 reference) and the one deviation (an all-zero file yields zeros, with a warning, where the reference divides by zero) are specified
@@ -33,6 +33,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from . import ragged
 from .preprocess import load_wav
 from .text import _clean
 
@@ -87,39 +88,15 @@ class _DeviceAudio:
     """audio_fn on the GPU: [float32 1-D] at sr_in -> [int16 1-D] at sr_out, peak-normalised; one H2D and one D2H copy per call."""
 
     def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("fastspeech2_amd.prepare_align resamples and normalises on an AMD GPU only (no CPU fallback): "
-                               "pass device='cuda' or an audio_fn")
-        self._staging = None
+        self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.prepare_align (without an audio_fn)")
+        self._staging = ragged.Staging()
 
     def __call__(self, wavs, sr_in, sr_out, max_wav_value):
         from . import resample as R
-        lens = [len(w) for w in wavs]
-        B, N = len(wavs), max(max(lens), 1)
-        if self._staging is None or self._staging.numel() < B * N:
-            self._staging = torch.empty(B * N, dtype=torch.float32).pin_memory()
-        host = self._staging[:B * N].view(B, N)
-        hv = host.numpy()
-        for b, w in enumerate(wavs):
-            hv[b, :lens[b]] = w
-        y, out_lens = R.resample_poly(host.to(self.device, non_blocking=True), lens, sr_in, sr_out)
+        self._staging.pack(wavs)
+        y, out_lens = R.resample_poly(self._staging.to(self.device), [len(w) for w in wavs], sr_in, sr_out)
         pcm = R.peaknorm_pcm(y, out_lens, R.peak_abs(y, out_lens), max_wav_value).cpu().numpy()   # orders after the kernels
         return [pcm[b, :n].copy() for b, n in enumerate(out_lens.tolist())]
-
-
-def _batches(lens, batch_samples):
-    """Longest first, then greedy packing under `batch_samples` of PADDED audio (rows x longest row), as Preprocessor._batches."""
-    order = sorted(range(len(lens)), key=lambda i: -lens[i])
-    batch, longest = [], 0
-    for i in order:
-        if batch and (len(batch) + 1) * max(longest, lens[i]) > batch_samples:
-            yield batch
-            batch, longest = [], 0
-        batch.append(i)
-        longest = max(longest, lens[i])
-    if batch:
-        yield batch
 
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
@@ -138,22 +115,18 @@ def prepare_align(config, device="cuda", audio_fn=None, batch_seconds=1500.0, nu
 
     def flush():
         nonlocal written
-        by_rate = {}
-        for k, (_, sr, _) in enumerate(window):
-            by_rate.setdefault(sr, []).append(k)
-        for sr in sorted(by_rate):                                          # a batch never mixes source rates: one filter per launch
-            idx = by_rate[sr]
-            for batch in _batches([len(window[k][2]) for k in idx], batch_samples * sr // sampling_rate):
-                ks = [idx[i] for i in batch]
-                pcms = audio_fn([window[k][2] for k in ks], sr, sampling_rate, max_wav_value)
-                for k, pcm in zip(ks, pcms):
-                    from scipy.io import wavfile
-                    pcm = np.asarray(pcm)
-                    assert pcm.dtype == np.int16 and pcm.ndim == 1, (pcm.dtype, pcm.shape)
-                    if not pcm.any():
-                        warnings.warn(f"{window[k][0]}: silent file written as zeros (the reference divides by a zero peak here)")
-                    wavfile.write(window[k][0], sampling_rate, pcm)
-                    written += 1
+        # a batch never mixes source rates (one filter per launch); its budget is `batch_seconds` at the source rate
+        for sr, ks in ragged.keyed_batches([w[1] for w in window], [(len(w[2]),) for w in window],
+                                           lambda sr: batch_samples * sr // sampling_rate, ragged.padded_samples):
+            pcms = audio_fn([window[k][2] for k in ks], sr, sampling_rate, max_wav_value)
+            for k, pcm in zip(ks, pcms):
+                from scipy.io import wavfile
+                pcm = np.asarray(pcm)
+                assert pcm.dtype == np.int16 and pcm.ndim == 1, (pcm.dtype, pcm.shape)
+                if not pcm.any():
+                    warnings.warn(f"{window[k][0]}: silent file written as zeros (the reference divides by a zero peak here)")
+                wavfile.write(window[k][0], sampling_rate, pcm)
+                written += 1
         window.clear()
 
     def read(entry):

@@ -14,9 +14,9 @@ processed in two stages so that the GPU sees few, large launches:
                 With `resample="gpu"` a file whose rate differs from the config's is no longer resampled here: the wav stays at
                 its own rate, the trim window is computed in OUTPUT samples exactly as above, and only the input span that
                 window depends on goes to the device stage.
-  device stage  utterances are packed, longest first, into ragged batches of up to `batch_seconds` of audio
-                (one pinned staging buffer -> one H2D copy -> reflect pad per row -> framed-DFT GEMM -> fused
-                |.| / mel / log / energy epilogue -> one D2H copy), `audio.TacotronSTFT.mel_spectrogram_ragged`.
+  device stage  utterances are packed into ragged batches of up to `batch_seconds` of padded audio (`ragged.greedy_batches`);
+                per batch: `ragged.Staging` -> one H2D copy -> reflect pad per row -> framed-DFT GEMM -> fused
+                |.| / mel / log / energy epilogue -> one D2H copy, `audio.TacotronSTFT.mel_spectrogram_ragged`.
                 With `resample="gpu"` batches hold one source rate and start with `resample.resample_poly` of each row's trim
                 window (csrc/fs2_resample.hip): its unclipped output feeds `pitch.dio_stonemask`, its clamped output the STFT,
                 without a round trip through the host.
@@ -45,7 +45,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import audio as Audio
+from . import audio as Audio, ragged
 
 SIL_PHONES = ("sil", "sp", "spn")
 
@@ -233,8 +233,8 @@ class Preprocessor:
             raise ValueError(f"pitch must be None or 'gpu', got {pitch!r}")
         if pitch == "gpu" and pitch_fn is not None:
             raise ValueError("pass either pitch_fn or pitch='gpu', not both")
-        if pitch == "gpu" and torch.device(device).type != "cuda":
-            raise RuntimeError("Preprocessor(pitch='gpu') runs DIO + StoneMask on an AMD GPU only (no CPU fallback)")
+        if pitch == "gpu":
+            ragged.require_device(torch.device(device), "Preprocessor(pitch='gpu'): DIO + StoneMask")
         self.config = config
         self.in_dir = config["path"]["raw_path"]
         self.out_dir = config["path"]["preprocessed_path"]
@@ -260,8 +260,7 @@ class Preprocessor:
         self.num_workers = num_workers
         self.host_chunk = max(64, 8 * num_workers)          # utterances handed to the host thread pool at a time
         self.seed = seed
-        self._staging = None
-        self._pitch_staging = None
+        self._staging = ragged.Staging()
 
     # ---------------------------------------------------------------- host stage
     def get_alignment(self, intervals):
@@ -318,87 +317,39 @@ class Preprocessor:
                 "duration": duration, "wav": wav, "pitch": pitch, **window}
 
     # ---------------------------------------------------------------- device stage
-    def _batches(self, items):
-        """Longest first, then greedy packing under `batch_samples` of PADDED audio (rows x longest row)."""
-        order = sorted(range(len(items)), key=lambda i: -len(items[i]["wav"]))
-        batch, longest = [], 0
-        for i in order:
-            n = len(items[i]["wav"])
-            if batch and (len(batch) + 1) * max(longest, n) > self.batch_samples:
-                yield batch
-                batch, longest = [], 0
-            batch.append(i)
-            longest = max(longest, n)
-        if batch:
-            yield batch
+    def _stage(self, wavs, clip=False):
+        """[float32 1-D] -> ((B, N) float32 on the device, lengths); one H2D copy (ragged.Staging)."""
+        ragged.require_device(self.device, "fastspeech2_amd.preprocess")
+        self._staging.pack(wavs, clip)
+        return self._staging.to(self.device), [len(w) for w in wavs]
 
-    def _rate_batches(self, items):
-        """resample="gpu": `_batches` within each source rate (one filter per launch)."""
-        by_rate = {}
-        for i, it in enumerate(items):
-            by_rate.setdefault(it["sr"], []).append(i)
-        for sr in sorted(by_rate):
-            idx = by_rate[sr]
-            for batch in self._batches([items[i] for i in idx]):
-                yield [idx[k] for k in batch]
+    def _features(self, mel, energy, frames):
+        mel, energy = mel.cpu().numpy(), energy.cpu().numpy()               # one D2H each; the copy orders after the kernels
+        return [(mel[b, :, :f].astype(np.float32), energy[b, :f].astype(np.float32)) for b, f in enumerate(frames.tolist())]
 
     def _extract_mels(self, wavs):
         """[float32 1-D] -> [(mel (n_mel, frames), energy (frames,))] float32 numpy; one ragged launch set on the GPU
         (audio/tools.py:8-15 `get_mel_from_wav` per utterance in the reference: clip to [-1, 1], STFT, squeeze)."""
-        if self.device.type != "cuda":
-            raise RuntimeError("fastspeech2_amd.preprocess runs its STFT on an AMD GPU only (no CPU fallback)")
-        lens = [len(w) for w in wavs]
-        B, N = len(wavs), max(lens)
-        if self._staging is None or self._staging.numel() < B * N:
-            self._staging = torch.empty(B * N, dtype=torch.float32).pin_memory()
-        host = self._staging[:B * N].view(B, N)
-        hv = host.numpy()
-        for b, w in enumerate(wavs):
-            np.clip(w, -1.0, 1.0, out=hv[b, :lens[b]])
-            hv[b, lens[b]:] = 0.0
-        y = host.to(self.device, non_blocking=True)
-        mel, energy, frames = self.STFT.mel_spectrogram_ragged(y, torch.tensor(lens, dtype=torch.int32))
-        mel, energy = mel.cpu().numpy(), energy.cpu().numpy()               # one D2H each; the copy orders after the kernels
-        return [(mel[b, :, :f].astype(np.float32), energy[b, :f].astype(np.float32))
-                for b, f in enumerate(frames.tolist())]
+        return self._features(*self.STFT.mel_spectrogram_ragged(*self._stage(wavs, clip=True)))
 
     def _extract_pitch(self, wavs):
         """pitch="gpu": [float32 1-D] -> [f0 per DIO frame, float64], DIO + StoneMask on the GPU over the UNCLIPPED audio (the
-        reference's pitch_fn sees the wav before get_mel_from_wav clips it); its own staging buffer, one H2D and one D2H copy."""
+        reference's pitch_fn sees the wav before get_mel_from_wav clips it); one H2D and one D2H copy."""
         from . import pitch as Pitch
-        lens = [len(w) for w in wavs]
-        B, N = len(wavs), max(lens)
-        if self._pitch_staging is None or self._pitch_staging.numel() < B * N:
-            self._pitch_staging = torch.empty(B * N, dtype=torch.float32).pin_memory()
-        hv = self._pitch_staging[:B * N].view(B, N)
-        for b, w in enumerate(wavs):
-            hv.numpy()[b, :lens[b]] = w
-        f0, _, frames = Pitch.dio_stonemask(hv.to(self.device, non_blocking=True), lens, self.sampling_rate,
-                                            self.hop_length / self.sampling_rate * 1000)
+        f0, _, frames = Pitch.dio_stonemask(*self._stage(wavs), self.sampling_rate, self.hop_length / self.sampling_rate * 1000)
         return [f0[b, :f] for b, f in enumerate(frames.tolist())]
 
     def _extract_resampled(self, its):
         """resample="gpu": host-stage items of ONE source rate -> ([f0 per DIO frame], [(mel, energy)]).  One H2D copy of the input
         spans, `resample_poly` of each row's trim window, then F0 on its unclipped and the STFT on its clamped output."""
         from . import pitch as Pitch, resample as R
-        if self.device.type != "cuda":
-            raise RuntimeError("fastspeech2_amd.preprocess runs its STFT on an AMD GPU only (no CPU fallback)")
-        lens = [len(it["wav"]) for it in its]
-        B, N = len(its), max(max(lens), 1)
-        if self._staging is None or self._staging.numel() < B * N:
-            self._staging = torch.empty(B * N, dtype=torch.float32).pin_memory()
-        host = self._staging[:B * N].view(B, N)
-        hv = host.numpy()
-        for b, it in enumerate(its):
-            hv[b, :lens[b]] = it["wav"]
-        y, yc, out_lens = R.resample_poly(host.to(self.device, non_blocking=True), lens, its[0]["sr"], self.sampling_rate,
+        x, lens = self._stage([it["wav"] for it in its])
+        y, yc, out_lens = R.resample_poly(x, lens, its[0]["sr"], self.sampling_rate,
                                           out_begin=[it["out_begin"] for it in its], out_len=[it["out_len"] for it in its],
                                           clip=True, in_begin=[it["in_begin"] for it in its])
         f0, _, f0_frames = Pitch.dio_stonemask(y, out_lens, self.sampling_rate, self.hop_length / self.sampling_rate * 1000)
-        mel, energy, frames = self.STFT.mel_spectrogram_ragged(yc, out_lens.to(torch.int32))
-        mel, energy = mel.cpu().numpy(), energy.cpu().numpy()
         return ([f0[b, :f] for b, f in enumerate(f0_frames.tolist())],
-                [(mel[b, :, :f].astype(np.float32), energy[b, :f].astype(np.float32)) for b, f in enumerate(frames.tolist())])
+                self._features(*self.STFT.mel_spectrogram_ragged(yc, out_lens)))
 
     # ---------------------------------------------------------------- per utterance, after the STFT
     def _finish_utterance(self, it, mel_spectrogram, energy):
@@ -463,7 +414,9 @@ class Preprocessor:
 
         def flush():
             items = [it for _, it in window]
-            for batch in (self._rate_batches(items) if self.resample == "gpu" else self._batches(items)):
+            # resample="gpu": a batch holds one source rate
+            for _, batch in ragged.keyed_batches([it.get("sr") for it in items], [(len(it["wav"]),) for it in items],
+                                                 lambda sr: self.batch_samples, ragged.padded_samples):
                 if self.resample == "gpu":
                     pitches, mels = self._extract_resampled([items[i] for i in batch])
                 else:

@@ -34,7 +34,7 @@ from math import gcd
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ragged
 
 MAX_FACTOR = 1 << 16                # keeps the tap table (about 21 max(up, down) doubles) small and the kernel's 32-bit phase arithmetic exact
 
@@ -87,29 +87,6 @@ def _device_table(dev, up, down):
     return _tables[key]
 
 
-def _ints(v, B, name):
-    v = [int(a) for a in (v.tolist() if isinstance(v, (torch.Tensor, np.ndarray)) else v)]
-    if len(v) != B:
-        raise ValueError(f"{name} must hold B={B} values, got {len(v)}")
-    return v
-
-
-def _check(x, lens, what):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError(f"fastspeech2_amd.resample.{what} runs on an AMD GPU only (no CPU fallback): pass a device tensor")
-    if x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError(f"{what}: expected a (B, N) float32 tensor, got {tuple(x.shape)} {x.dtype}")
-    x = x.contiguous()
-    lens_h = _ints(lens, x.shape[0], "lens")
-    if any(n < 0 or n > x.shape[1] for n in lens_h):
-        raise ValueError(f"lens must lie in [0, {x.shape[1]}], got {lens_h}")
-    return x, lens_h
-
-
-def _i32(v, dev):
-    return torch.tensor(v, dtype=torch.int32, device=dev)
-
-
 def resample_poly(x, lens, sr_in, sr_out, out_begin=None, out_len=None, clip=False, in_begin=None):
     """Polyphase resampling of a ragged batch: x (B, N) float32 on the GPU, row b holds lens[b] samples at rate sr_in.
     Returns (y, out_lens) or, with clip=True, (y, y clamped to [-1, 1], out_lens): y (B, max(out_lens)) float32 on the device,
@@ -119,28 +96,25 @@ def resample_poly(x, lens, sr_in, sr_out, out_begin=None, out_len=None, clip=Fal
     row's full result (default: all ceil(lens[b] * up / down) of them).  `in_begin` says that row b holds the samples
     [in_begin[b], in_begin[b] + lens[b]) of its utterance and everything else counts as zero: hand over only the span a window
     needs (`input_span`); `out_begin` and `out_len` are then required.  sr_in == sr_out without a window or clip returns (x, lens)."""
-    x, lens_h = _check(x, lens, "resample_poly")
+    x, lens_h, _ = ragged.rows(x, lens, "fastspeech2_amd.resample.resample_poly", device_lens=False)
     B, N = x.shape
     up, down = ratio(sr_in, sr_out)
     if in_begin is not None and (out_begin is None or out_len is None):
         raise ValueError("in_begin needs out_begin and out_len: the utterance's full length is not known from a slice")
     if up == down and out_begin is None and out_len is None and not clip and in_begin is None:
         return x, torch.tensor(lens_h, dtype=torch.int64)
-    ob = _ints(out_begin, B, "out_begin") if out_begin is not None else [0] * B
-    ib = _ints(in_begin, B, "in_begin") if in_begin is not None else [0] * B
-    if out_len is not None:
-        ol = _ints(out_len, B, "out_len")
-    else:
-        ol = [max(out_length(n, up, down) - o, 0) for n, o in zip(lens_h, ob)]
-    if any(v < 0 or v >= 1 << 31 for v in ob + ol + ib):
-        raise ValueError(f"out_begin / out_len / in_begin must be non-negative 32-bit values, got {ob} {ol} {ib}")
+    cap = (1 << 31) - 1                                                       # the kernel's row arithmetic is 32-bit
+    ob = ragged.lengths(out_begin if out_begin is not None else [0] * B, B, cap, "out_begin")
+    ib = ragged.lengths(in_begin if in_begin is not None else [0] * B, B, cap, "in_begin")
+    ol = ragged.lengths(out_len if out_len is not None else [max(out_length(n, up, down) - o, 0) for n, o in zip(lens_h, ob)],
+                        B, cap, "out_len")
     dev = x.device
     tab, half, T = _device_table(dev, up, down)
     Nout = max(ol) if ol else 0
     y = torch.empty(B, Nout, dtype=torch.float32, device=dev)
     yc = torch.empty_like(y) if clip else None
     if B and Nout:
-        meta = _i32([ib, lens_h, ob, ol], dev)                                # one H2D copy; alive until the launch is queued
+        meta = torch.tensor([ib, lens_h, ob, ol], dtype=torch.int32, device=dev)       # one H2D copy; alive until the launch is queued
         ib_d, il_d, ob_d, ol_d = (meta[k].data_ptr() for k in range(4))
         _lib.call("fs2_resample_poly", x.data_ptr(), N, ib_d if in_begin is not None else None, il_d, tab.data_ptr(), up, down,
                   half, T, ob_d if out_begin is not None else None, ol_d, y.data_ptr(), yc.data_ptr() if clip else None, Nout,
@@ -161,9 +135,8 @@ def input_span(out_begin, out_len, n_in, up, down):
 
 def peak_abs(y, lens):
     """peak[b] = max |y[b, :lens[b]]| as a (B,) float32 device tensor (0 for an empty row)."""
-    y, lens_h = _check(y, lens, "peak_abs")
+    y, _, lens_d = ragged.rows(y, lens, "fastspeech2_amd.resample.peak_abs")
     peak = torch.empty(y.shape[0], dtype=torch.float32, device=y.device)
-    lens_d = _i32(lens_h, y.device)
     _lib.call("fs2_peak_abs", y.data_ptr(), y.shape[1], lens_d.data_ptr(), peak.data_ptr(), y.shape[0], y.shape[1], ops._stream())
     return peak
 
@@ -171,11 +144,11 @@ def peak_abs(y, lens):
 def peaknorm_pcm(y, lens, peak, max_wav_value):
     """int16(y / peak * max_wav_value) per row (see the module docstring for the cast and the peak == 0 rule): (B, N) int16 on the
     device, zero beyond lens[b]."""
-    y, lens_h = _check(y, lens, "peaknorm_pcm")
+    y, _, lens_d = ragged.rows(y, lens, "fastspeech2_amd.resample.peaknorm_pcm")
     if not isinstance(peak, torch.Tensor) or peak.device != y.device or peak.dtype != torch.float32 or peak.numel() != y.shape[0]:
         raise ValueError("peak must be a (B,) float32 tensor on y's device")
     pcm = torch.empty(y.shape, dtype=torch.int16, device=y.device)
-    lens_d, peak = _i32(lens_h, y.device), peak.contiguous()
+    peak = peak.contiguous()
     _lib.call("fs2_peaknorm_pcm", y.data_ptr(), y.shape[1], lens_d.data_ptr(), peak.data_ptr(), float(max_wav_value), pcm.data_ptr(),
               y.shape[1], y.shape[0], y.shape[1], ops._stream())
     return pcm
