@@ -11,6 +11,14 @@
     else if ((dtype) == FS2_BF16) { typedef bf16_t T; __VA_ARGS__; } \
     else { fs2_set_error("unsupported dtype %d", (int)(dtype)); return FS2_EDTYPE; }
 
+// the float4 a st4<T> followed by an ld4<T> gives back (bf16: round to nearest even; fp32: unchanged)
+template <typename T> __device__ __forceinline__ float4 rnd4(float4 v);
+template <> __device__ __forceinline__ float4 rnd4<float>(float4 v) { return v; }
+template <> __device__ __forceinline__ float4 rnd4<bf16_t>(float4 v) {
+    const uint32_t a = pack_bf16x2(v.x, v.y), b = pack_bf16x2(v.z, v.w);
+    return make_float4(__uint_as_float(a << 16), __uint_as_float(a & 0xffff0000u), __uint_as_float(b << 16), __uint_as_float(b & 0xffff0000u));
+}
+
 // ------------------------------------------------------------------ embedding + PE
 // one 64-lane wave per row, float4 per lane-iteration.
 template <typename T>
@@ -352,6 +360,51 @@ extern "C" int fs2_lr_gather_bwd(const void* dy, const int32_t* cum, void* dx, i
     if (rows == 0) return FS2_OK;
     DISPATCH_DTYPE(dtype, lr_gather_bwd_kernel<T><<<fs2_cdiv(rows, 4), 256, 0, stream>>>((const T*)dy, cum, (T*)dx, rows, L, Tm, C, accumulate));
     FS2_CHECK_LAUNCH("lr_gather_bwd");
+    return FS2_OK;
+}
+
+// The same segment sum followed by the two residual adds of the variance adaptor's backward, in one launch:
+//   dx0 = sum (stored in T)   dx1 = dx0 + add1   dx2 = dx1 + add2      (add2 optional; then dx2 is not written)
+// Each stage is rounded to T before the next add reads it, i.e. bit for bit what fs2_lr_gather_bwd + fs2_add (+ fs2_add) store.
+// All three are outputs because the embedding-gradient launches between the adds read the intermediate tensors.
+template <typename T>
+__global__ void lr_gather_bwd_add_kernel(const T* __restrict__ dy, const int32_t* __restrict__ cum, const T* __restrict__ add1,
+                                         const T* __restrict__ add2, T* __restrict__ dx0, T* __restrict__ dx1, T* __restrict__ dx2,
+                                         int rows, int L, int Tm, int C) {
+    int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // row = b*L + i
+    if (row >= rows) return;
+    int lane = threadIdx.x & 63;
+    int b = row / L, i = row - b * L;
+    int t0 = cum[(size_t)b * (L + 1) + i], t1 = cum[(size_t)b * (L + 1) + i + 1];
+    t0 = min(t0, Tm); t1 = min(t1, Tm);
+    const size_t o = (size_t)row * C;
+    for (int c = lane * 4; c < C; c += 256) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int t = t0; t < t1; ++t) {
+            float4 v = ld4<T>(dy + ((size_t)b * Tm + t) * C + c);
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        st4<T>(dx0 + o + c, s);
+        s = rnd4<T>(s);
+        float4 y = ld4<T>(add1 + o + c);
+        s = make_float4(s.x + y.x, s.y + y.y, s.z + y.z, s.w + y.w);
+        st4<T>(dx1 + o + c, s);
+        if (add2) {
+            s = rnd4<T>(s);
+            y = ld4<T>(add2 + o + c);
+            st4<T>(dx2 + o + c, make_float4(s.x + y.x, s.y + y.y, s.z + y.z, s.w + y.w));
+        }
+    }
+}
+extern "C" int fs2_lr_gather_bwd_add(const void* dy, const int32_t* cum, const void* add1, const void* add2, void* dx0, void* dx1,
+                                     void* dx2, int B, int L, int Tm, int C, int dtype, hipStream_t stream) {
+    FS2_CHECK_ARG(dy && cum && add1 && dx0 && dx1 && (!add2 || dx2), "lr_gather_bwd_add: null pointer");
+    FS2_CHECK_ARG((C % 4) == 0, "lr_gather_bwd_add: C%%4");
+    int rows = B * L;
+    if (rows == 0) return FS2_OK;
+    DISPATCH_DTYPE(dtype, lr_gather_bwd_add_kernel<T><<<fs2_cdiv(rows, 4), 256, 0, stream>>>(
+                              (const T*)dy, cum, (const T*)add1, (const T*)add2, (T*)dx0, (T*)dx1, (T*)dx2, rows, L, Tm, C));
+    FS2_CHECK_LAUNCH("lr_gather_bwd_add");
     return FS2_OK;
 }
 

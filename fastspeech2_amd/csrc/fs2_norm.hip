@@ -580,6 +580,7 @@ struct BnArgs {
     int M, C, cprp, rows_per_block, act;
     int cblk;                    // channels per workgroup (grid.y walks the channel blocks); cprp * V when one workgroup spans the row
     float p; uint64_t seed; const uint64_t* seed_dev;
+    float* out32; float* res32;  // MODE 4: fp32 images of the stored result / of the residual operand (out may then be NULL)
 };
 
 // tanh through one v_exp_f32 and one v_rcp_f32 (|error| < 3e-7 absolute; tanhf's branchy polynomial costs ~3x as much
@@ -594,6 +595,8 @@ __device__ __forceinline__ float fs2_tanh(float x) {
 }
 
 // MODE 0: statistics   1: apply   2: backward pass 1 (sums)   3: backward pass 2 (dx)
+// MODE 4: apply, the result ALSO (or only) written as fp32 - the value rounded to T first, i.e. bit for bit what a cast launch makes
+//         of the stored tensor - and the residual operand widened into res32 on the way (the model's fp32 outputs, fs2_bn_apply_out32).
 // Reducing modes (0, 2) run FEW fat workgroups (NT = 1024 threads, 4 rows in flight per thread).  Streaming modes (1, 3) use
 // many 256-thread workgroups.
 // The column sums are BIT-REPRODUCIBLE (r04): a workgroup stores its partial sums into its own row of a slab and a tiny second
@@ -616,6 +619,11 @@ template <typename T, int V> __device__ __forceinline__ void bn_stv(T* p, const 
     if constexpr (V == 8) { *reinterpret_cast<uint4*>(p) = pack8f(f); }
     else st4<T>(p, make_float4(f[0], f[1], f[2], f[3]));
 }
+
+// the fp32 value a store to T followed by a load gives back
+template <typename T> __device__ __forceinline__ float bn_round(float v);
+template <> __device__ __forceinline__ float bn_round<float>(float v) { return v; }
+template <> __device__ __forceinline__ float bn_round<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
 template <typename T, int MODE, int NT, int V>
 __global__ void __launch_bounds__(NT) bn_rows_kernel(BnArgs a) {
@@ -653,7 +661,7 @@ __global__ void __launch_bounds__(NT) bn_rows_kernel(BnArgs a) {
         if (MODE == 0) {
 #pragma unroll
             for (int k = 0; k < V; ++k) { float d = v[k] - mu[k]; a1[k] += d; a2[k] += d * d; }
-        } else if (MODE == 1) {
+        } else if (MODE == 1 || MODE == 4) {
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 float o = (v[k] - mu[k]) * rs[k] * gm[k] + bt[k];
@@ -666,8 +674,18 @@ __global__ void __launch_bounds__(NT) bn_rows_kernel(BnArgs a) {
                 bn_ldv<T, V>(res + e, r4);
 #pragma unroll
                 for (int k = 0; k < V; ++k) v[k] += r4[k];
+                if (MODE == 4 && a.res32) {
+#pragma unroll
+                    for (int k = 0; k < V; k += 4) *reinterpret_cast<float4*>(a.res32 + e + k) = make_float4(r4[k], r4[k + 1], r4[k + 2], r4[k + 3]);
+                }
             }
-            bn_stv<T, V>(out + e, v);
+            if (MODE == 1 || out) bn_stv<T, V>(out + e, v);
+            if (MODE == 4) {
+#pragma unroll
+                for (int k = 0; k < V; ++k) v[k] = bn_round<T>(v[k]);
+#pragma unroll
+                for (int k = 0; k < V; k += 4) *reinterpret_cast<float4*>(a.out32 + e + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < V; ++k) {
@@ -915,6 +933,28 @@ extern "C" int fs2_bn_apply(const void* x, const float* mean_rstd, const float* 
     dim3 grid = bn_geometry(a, M, C, 256, 2048, vec);
     BN_LAUNCH(1, 256, grid);
     FS2_CHECK_LAUNCH("bn_apply");
+    return FS2_OK;
+}
+
+// fs2_bn_apply that also writes fp32 images: out32 [M][C] = the result as stored in `dtype`, widened (what fs2_cast makes of `out`);
+// res32 [M][C] (optional, needs res) = the residual operand widened.  out may be NULL when only the fp32 image is wanted.  The last
+// PostNet layer uses it: its result and its residual (the mel-linear output) are the model's two fp32 outputs, which cost two cast
+// launches at the end of the forward chain before.
+extern "C" int fs2_bn_apply_out32(const void* x, const float* mean_rstd, const float* gamma, const float* beta, const void* res,
+                                  void* out, float* out32, float* res32, int M, int C, int act, float p, uint64_t seed,
+                                  const uint64_t* seed_dev, int dtype, hipStream_t stream) {
+    FS2_CHECK_ARG(x && mean_rstd && gamma && beta && out32, "bn_apply_out32: null pointer");
+    FS2_CHECK_ARG(!res32 || res, "bn_apply_out32: res32 without res");
+    FS2_CHECK_ARG(C % 4 == 0 && C <= 1024, "bn_apply_out32: C=%d must be a multiple of 4, <= 1024", C);
+    FS2_CHECK_ARG((((uintptr_t)out32 | (uintptr_t)res32) & 15) == 0, "bn_apply_out32: fp32 outputs must be 16-byte aligned");
+    if ((size_t)M * C == 0) return FS2_OK;
+    BnArgs a = {};
+    a.x = x; a.res = res; a.out = out; a.mean_rstd = mean_rstd; a.gamma = gamma; a.beta = beta; a.act = act; a.p = p;
+    a.seed = seed; a.seed_dev = seed_dev; a.out32 = out32; a.res32 = res32;
+    const int vec = bn_vec(a, C, dtype);
+    dim3 grid = bn_geometry(a, M, C, 256, 2048, vec);
+    BN_LAUNCH(4, 256, grid);
+    FS2_CHECK_LAUNCH("bn_apply_out32");
     return FS2_OK;
 }
 

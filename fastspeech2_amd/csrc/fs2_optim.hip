@@ -24,6 +24,7 @@ __global__ void __launch_bounds__(256) sumsq_partial_kernel(const float* __restr
     __syncthreads();
     if (threadIdx.x == 0) ws[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
 }
+template <bool SET>
 __global__ void __launch_bounds__(256) sumsq_final_kernel(const float* __restrict__ ws, int nblocks, float* __restrict__ out) {
     __shared__ float s[4];
     float acc = 0.f;
@@ -31,20 +32,33 @@ __global__ void __launch_bounds__(256) sumsq_final_kernel(const float* __restric
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) out[0] += (s[0] + s[1]) + (s[2] + s[3]);
+    if (threadIdx.x == 0) {
+        const float t = (s[0] + s[1]) + (s[2] + s[3]);
+        out[0] = SET ? t : out[0] + t;
+    }
 }
 // out[0] += sum x^2   (caller zeroes out; ws = FS2_SUMSQ_BLOCKS floats of workspace)
-extern "C" int fs2_sumsq(const float* x, size_t n, float* out, float* ws, hipStream_t stream) {
+static int sumsq_launch(const float* x, size_t n, float* out, float* ws, bool set, hipStream_t stream) {
     FS2_CHECK_ARG(x && out && ws, "sumsq: null pointer");
     FS2_CHECK_ARG(((uintptr_t)x & 15) == 0, "sumsq: x must be 16-byte aligned");
+    if (n == 0 && set) { (void)hipMemsetAsync(out, 0, sizeof(float), stream); return FS2_OK; }
     if (n == 0) return FS2_OK;
     size_t blocks = (n / 4 + 255) / 256;
     if (blocks > FS2_SUMSQ_BLOCKS) blocks = FS2_SUMSQ_BLOCKS;
     if (blocks == 0) blocks = 1;
     sumsq_partial_kernel<<<(unsigned)blocks, 256, 0, stream>>>(x, n, ws);
-    sumsq_final_kernel<<<1, 256, 0, stream>>>(ws, (int)blocks, out);
+    if (set) sumsq_final_kernel<true><<<1, 256, 0, stream>>>(ws, (int)blocks, out);
+    else sumsq_final_kernel<false><<<1, 256, 0, stream>>>(ws, (int)blocks, out);
     FS2_CHECK_LAUNCH("sumsq");
     return FS2_OK;
+}
+extern "C" int fs2_sumsq(const float* x, size_t n, float* out, float* ws, hipStream_t stream) {
+    return sumsq_launch(x, n, out, ws, false, stream);
+}
+// out[0] = sum x^2: the final block STORES (0 + t == t bit for bit), so the caller's clear of `out` - one fill launch per
+// optimiser step in front of the norm - is not needed.
+extern "C" int fs2_sumsq_set(const float* x, size_t n, float* out, float* ws, hipStream_t stream) {
+    return sumsq_launch(x, n, out, ws, true, stream);
 }
 
 // hyper = {lr, bias_correction1, bias_correction2, grad_scale_extra}
@@ -56,13 +70,15 @@ extern "C" int fs2_sumsq(const float* x, size_t n, float* out, float* ws, hipStr
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, size_t n4, const float* __restrict__ gnorm_sq,
                                                    float max_norm, const float* __restrict__ hyper, float b1, float b2, float eps,
-                                                   float wd, bf16_t* __restrict__ p_lowp, int zero_grad) {
+                                                   float wd, bf16_t* __restrict__ p_lowp, int zero_grad, float lr_h, float bc1_h,
+                                                   float bc2_h) {
     float coef = 1.f;
     if (gnorm_sq && max_norm > 0.f) {
         float nrm = sqrtf(gnorm_sq[0]);
         coef = fminf(1.f, max_norm / (nrm + 1e-6f));
     }
-    const float lr = hyper[0], bc1 = hyper[1], bc2 = hyper[2];
+    // hyper == NULL: the step's scalars came with the launch (fs2_adam_step_h)
+    const float lr = hyper ? hyper[0] : lr_h, bc1 = hyper ? hyper[1] : bc1_h, bc2 = hyper ? hyper[2] : bc2_h;
     const float step = lr / bc1, rbc2 = rsqrtf(bc2);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         float4 g4 = reinterpret_cast<const float4*>(g)[i], p4 = reinterpret_cast<const float4*>(p)[i];
@@ -85,10 +101,10 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float*
         if (zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
-extern "C" int fs2_adam_step(float* p, float* g, float* m, float* v, size_t n, const float* gnorm_sq, float max_norm,
-                             const float* hyper, float b1, float b2, float eps, float wd, void* p_lowp, int lowp_dtype,
-                             int zero_grad, hipStream_t stream) {
-    FS2_CHECK_ARG(p && g && m && v && hyper, "adam_step: null pointer");
+static int adam_launch(float* p, float* g, float* m, float* v, size_t n, const float* gnorm_sq, float max_norm,
+                       const float* hyper, float lr, float bc1, float bc2, float b1, float b2, float eps, float wd, void* p_lowp,
+                       int lowp_dtype, int zero_grad, hipStream_t stream) {
+    FS2_CHECK_ARG(p && g && m && v, "adam_step: null pointer");
     FS2_CHECK_ARG(n % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
                   "adam_step: flat buffers must be 16-byte aligned with n %% 4 == 0 (n=%zu)", n);
     FS2_CHECK_ARG(!p_lowp || lowp_dtype == FS2_BF16, "adam_step: the low-precision parameter copy must be bf16");
@@ -96,7 +112,22 @@ extern "C" int fs2_adam_step(float* p, float* g, float* m, float* v, size_t n, c
     size_t n4 = n / 4;
     size_t blocks = (n4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    adam_kernel<<<(unsigned)blocks, 256, 0, stream>>>(p, g, m, v, n4, gnorm_sq, max_norm, hyper, b1, b2, eps, wd, (bf16_t*)p_lowp, zero_grad);
+    adam_kernel<<<(unsigned)blocks, 256, 0, stream>>>(p, g, m, v, n4, gnorm_sq, max_norm, hyper, b1, b2, eps, wd, (bf16_t*)p_lowp, zero_grad,
+                                                      lr, bc1, bc2);
     FS2_CHECK_LAUNCH("adam_step");
     return FS2_OK;
+}
+extern "C" int fs2_adam_step(float* p, float* g, float* m, float* v, size_t n, const float* gnorm_sq, float max_norm,
+                             const float* hyper, float b1, float b2, float eps, float wd, void* p_lowp, int lowp_dtype,
+                             int zero_grad, hipStream_t stream) {
+    FS2_CHECK_ARG(hyper, "adam_step: null pointer");
+    return adam_launch(p, g, m, v, n, gnorm_sq, max_norm, hyper, 0.f, 1.f, 1.f, b1, b2, eps, wd, p_lowp, lowp_dtype, zero_grad, stream);
+}
+// The same with lr and the two bias corrections as LAUNCH ARGUMENTS (the fp32 values the device vector would hold): an eager step
+// needs no host-to-device copy of three floats in front of the optimiser - the copy launch that sat at every step boundary.  A
+// captured graph keeps fs2_adam_step (its replays read fresh values from device memory).
+extern "C" int fs2_adam_step_h(float* p, float* g, float* m, float* v, size_t n, const float* gnorm_sq, float max_norm, float lr,
+                               float bc1, float bc2, float b1, float b2, float eps, float wd, void* p_lowp, int lowp_dtype,
+                               int zero_grad, hipStream_t stream) {
+    return adam_launch(p, g, m, v, n, gnorm_sq, max_norm, nullptr, lr, bc1, bc2, b1, b2, eps, wd, p_lowp, lowp_dtype, zero_grad, stream);
 }

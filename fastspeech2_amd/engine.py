@@ -40,6 +40,33 @@ class _Saved:
     pass
 
 
+class _GradSink:
+    """Hand-over of d mel / d postnet-mel from the fused loss to Engine.backward, beside autograd: the loss kernel writes them in the
+    compute dtype and the [B*T, n_mel] row layout the PostNet backward reads (fs2_loss_bwd_lp), where autograd would carry fp32
+    tensors that have to be converted first.  Engine.run attaches one to the two mel outputs of a bf16 training forward;
+    FastSpeech2Loss claims it (once: only one loss can own the hand-over) and its backward fills it; Engine.backward takes what is
+    there and adds whatever gradient autograd delivered on top (a second loss on the same outputs)."""
+
+    def __init__(self, dtype):
+        self.dtype = dtype
+        self.claimed = False
+        self.dmel = self.dpost = None
+
+    def claim(self):
+        if self.claimed:
+            return False
+        self.claimed = True
+        return True
+
+    def put(self, dmel, dpost):
+        self.dmel, self.dpost = dmel, dpost
+
+    def take(self):
+        r = (self.dmel, self.dpost)
+        self.dmel = self.dpost = None
+        return r
+
+
 class Engine:
     def __init__(self, model, device):
         self.m = model
@@ -582,6 +609,8 @@ class Engine:
         # the valid-position counts the loss normalises by came out of the same launches as the masks: hand them over on the
         # tensor the loss receives (FastSpeech2Loss falls back to computing them when the attribute is absent)
         st.mel_lens_out._fs2_counts = (st.counts, src_lens, max_src_len, st.Tdec)
+        if need_grad and st.sink is not None:
+            mel._fs2_sink = post._fs2_sink = st.sink
         return (mel, post, p_pred, e_pred, logd, st.d_rounded, st.src_masks, st.mel_masks, src_lens, st.mel_lens_out)
 
     def forward(self, st):
@@ -725,11 +754,17 @@ class Engine:
             c = self._gemm(W, pre + "0.conv", h, Tdec, taps=5, pad=2)
             act = ACT_TANH if i < 4 else ACT_NONE
             res = mel if i == 4 else None
+            # the last layer's result and its residual operand (the mel-linear output) are the model's two fp32 outputs: in a
+            # low-precision run that layer's apply pass stores them as fp32 itself (no cast launches behind the PostNet)
+            out32 = i == 4 and cdt != torch.float32
             if training:
                 h_out, mean_rstd = ops.bn_train_fwd(c, P[pre + "1.weight"], P[pre + "1.bias"], self.Bf[pre + "1.running_mean"],
                                                     self.Bf[pre + "1.running_var"], act, p_pn, _seed_pair(200 + i, seed_dev)[0], res=res,
                                                     seed_dev=_seed_pair(200 + i, seed_dev)[1], ws=self._bn_workspace(c.shape[1])[0],
-                                                    num_batches_tracked=self.Bf[pre + "1.num_batches_tracked"])
+                                                    num_batches_tracked=self.Bf[pre + "1.num_batches_tracked"], out32=out32)
+            elif out32:
+                mean_rstd = self._bn_eval_stats(pre)
+                h_out = ops.bn_apply_out32(c, mean_rstd, P[pre + "1.weight"], P[pre + "1.bias"], res, act, 0.0, 0)[1:]
             else:
                 mean_rstd = self._bn_eval_stats(pre)
                 h_out = torch.empty_like(c)
@@ -747,9 +782,11 @@ class Engine:
             self._branch_main.wait_stream(self._side_stream)
             self._pack_pending = False              # (that join covers the data-gradient packs too)
         n_mel = mel.shape[1]
-        mel_o = (ops.cast(mel, torch.float32) if cdt != torch.float32 else mel).view(B, Tdec, n_mel)
-        post_o = (ops.cast(post, torch.float32) if cdt != torch.float32 else post).view(B, Tdec, n_mel)
+        post_o, mel_o = post if cdt != torch.float32 else (post, mel)      # (low precision: the last apply pass wrote both as fp32)
+        mel_o, post_o = mel_o.view(B, Tdec, n_mel), post_o.view(B, Tdec, n_mel)
+        st.sink = _GradSink(cdt) if (keep and cdt != torch.float32) else None
         if keep:
+            sv.sink = st.sink
             sv.W, sv.B, sv.L, sv.T = W, B, L, Tdec
             sv.src_lens32, sv.dec_lens32, sv.cum, sv.seed_dev = src_lens32, dec_lens32, cum, seed_dev
             sv.dec_out, sv.texts, sv.speakers = y, st.texts, st.speakers
@@ -797,6 +834,11 @@ class Engine:
                     t.record_stream(self._main)
         dmel = to_c(dmel, (B * T, n_mel))
         dpost = to_c(dpost, (B * T, n_mel))
+        if sv.sink is not None:                     # the fused loss wrote its two mel gradients in the compute dtype (see _GradSink)
+            s_dmel, s_dpost = sv.sink.take()
+            if s_dmel is not None:
+                dmel = s_dmel if dmel is None else ops.add(dmel, s_dmel)
+                dpost = s_dpost if dpost is None else ops.add(dpost, s_dpost)
         zeros = None
         if dmel is None or dpost is None:
             zeros = torch.zeros(B * T, n_mel, device=self.device, dtype=cdt)
@@ -838,9 +880,21 @@ class Engine:
             ops.bucket_embed_bwd(sv.pitch_idx, dy, G["variance_adaptor.pitch_embedding.weight"])
             if dpp is not None:
                 dy = self._pred_bwd(W, G, "pitch", sv.pitch, dpp, B, seed_dev, dy)
-        dx = ops.lr_gather_bwd(dy, sv.cum, B, L, T)
+        fold = ev_e is not None and dv_e is not None and dv_pd is not None
+        if fold:
+            # the two adds of the predictors' input gradients ride on the length regulator's backward (one launch writes the three
+            # stages the embedding-gradient launches and the encoder read, rounded as the separate launches rounded them)
+            self._main.wait_event(ev_e)
+            self._main.wait_event(ev_pd)
+            dx0, dx1, dx = ops.lr_gather_bwd_add(dy, sv.cum, dv_e, dv_pd, B, L, T)
+            ops.bucket_embed_bwd(sv.energy_idx, dx0, G["variance_adaptor.energy_embedding.weight"])
+            ops.bucket_embed_bwd(sv.pitch_idx, dx1, G["variance_adaptor.pitch_embedding.weight"])
+        else:
+            dx = ops.lr_gather_bwd(dy, sv.cum, B, L, T)
         # ---- phoneme-level variance branches
-        if ev_e is not None:                        # the predictors' input gradients were computed on the side stream
+        if fold:
+            pass
+        elif ev_e is not None:                      # the predictors' input gradients were computed on the side stream
             ops.bucket_embed_bwd(sv.energy_idx, dx, G["variance_adaptor.energy_embedding.weight"])
             if dv_e is not None:
                 self._main.wait_event(ev_e)
@@ -885,6 +939,7 @@ class _FS2Function(torch.autograd.Function):
     def forward(ctx, engine, st, *params):
         outs, sv = engine.forward(st)
         ctx.engine, ctx.sv, ctx.n = engine, sv, len(params)
+        ctx.set_materialize_grads(False)    # an output nobody differentiated arrives as None, not as a zero tensor to fill and convert
         return outs
 
     @staticmethod

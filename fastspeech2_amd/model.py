@@ -362,22 +362,36 @@ class FastSpeech2(nn.Module):
 
 
 class _FusedLoss(torch.autograd.Function):
-    """All five loss terms in one pass over the padded tensors (fs2_loss_fwd), gradients in one more (fs2_loss_bwd)."""
+    """All five loss terms in one pass over the padded tensors (fs2_loss_fwd), gradients in one more (fs2_loss_bwd_lp).  The six
+    values leave as six outputs, so backward receives one factor per term (None for the terms nobody differentiated) and hands
+    their device pointers to the kernel: nothing assembles a six-element gradient vector (autograd's unbind backward did, with
+    five zero fills and a concatenation per step).
+    sink: the engine's gradient hand-over (Engine.run attaches it to the mel outputs it returns) or None.  With a sink, d mel and
+    d postnet-mel are written ONCE, in the model's compute dtype and row layout, straight into the sink; autograd carries no
+    gradient for those two (it would hand the engine fp32 tensors to convert)."""
 
     @staticmethod
-    def forward(ctx, mel, post, p_pred, e_pred, logd, mel_t, mel_lens, src_lens, p_t, e_t, dur, cnt, p_frame, e_frame):
+    def forward(ctx, mel, post, p_pred, e_pred, logd, mel_t, mel_lens, src_lens, p_t, e_t, dur, cnt, p_frame, e_frame, sink):
         mel, post, p_pred, e_pred, logd = (t.contiguous() for t in (mel, post, p_pred, e_pred, logd))
         losses = ops.loss_fwd(mel, post, mel_t, mel_lens, src_lens, p_pred, p_t, e_pred, e_t, logd, dur, cnt, p_frame, e_frame)
         ctx.save_for_backward(mel, post, p_pred, e_pred, logd, mel_t, mel_lens, src_lens, p_t, e_t, dur, cnt)
         ctx.flags = (p_frame, e_frame)
-        return losses
+        ctx.sink = sink
+        ctx.set_materialize_grads(False)
+        return tuple(losses.unbind(0))
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, *gs):
         mel, post, p_pred, e_pred, logd, mel_t, mel_lens, src_lens, p_t, e_t, dur, cnt = ctx.saved_tensors
-        grads = ops.loss_bwd(mel, post, mel_t, mel_lens, src_lens, p_pred, p_t, e_pred, e_t, logd, dur, cnt,
-                             g.contiguous().float(), *ctx.flags)
-        return grads + (None,) * 9
+        gs = [None if g is None else (g if g.dtype == torch.float32 else g.float()).contiguous() for g in gs]
+        sink = ctx.sink
+        grads = ops.loss_bwd_lp(mel, post, mel_t, mel_lens, src_lens, p_pred, p_t, e_pred, e_t, logd, dur, cnt, gs, *ctx.flags,
+                                grad_dtype=sink.dtype if sink is not None else torch.float32)
+        if sink is not None:
+            sink.put(grads[0], grads[1])
+            return (None, None) + grads[2:] + (None,) * 10
+        B, T, n_mel = mel.shape
+        return (grads[0].view(B, T, n_mel), grads[1].view(B, T, n_mel)) + grads[2:] + (None,) * 10
 
 
 class FastSpeech2Loss(nn.Module):
@@ -415,10 +429,14 @@ class FastSpeech2Loss(nn.Module):
         e_t = energy_targets.float() if energy_targets.dtype != torch.float32 else energy_targets
         dur = duration_targets if duration_targets.dtype == torch.int64 else duration_targets.long()
         assert p_t.stride(1) == 1 and e_t.stride(1) == 1 and dur.stride(1) == 1
-        losses = _FusedLoss.apply(mel_pred, post_pred, pitch_pred, energy_pred, logd_pred, mel_t, mel_lens, src_lens, p_t, e_t,
-                                  dur, counts, self.pitch_feature_level != "phoneme_level",
-                                  self.energy_feature_level != "phoneme_level")
-        return tuple(losses.unbind(0))
+        # the engine's own output tensors carry its gradient hand-over; the first loss computed from them takes it (a second one,
+        # or a loss on any other tensor, sends its gradient through autograd as before)
+        sink = getattr(mel_pred, "_fs2_sink", None)
+        if sink is None or sink is not getattr(post_pred, "_fs2_sink", None) or not sink.claim():
+            sink = None
+        return _FusedLoss.apply(mel_pred, post_pred, pitch_pred, energy_pred, logd_pred, mel_t, mel_lens, src_lens, p_t, e_t,
+                                dur, counts, self.pitch_feature_level != "phoneme_level",
+                                self.energy_feature_level != "phoneme_level", sink)
 
 
 class ScheduledOptim:
@@ -479,8 +497,9 @@ class ScheduledOptim:
         self._adam_step += 1
         lr = self.init_lr * self._get_lr_scale()
         b1, b2 = self.betas
-        self.set_hyper(lr, 1 - b1 ** self._adam_step, 1 - b2 ** self._adam_step)
-        self.apply_update(zero_grad=zero_grad)
+        # eager step: the three scalars ride in the Adam launch's arguments (a captured graph reads them from device memory:
+        # set_hyper + apply_update, bench.capture_graph)
+        self.apply_update(zero_grad=zero_grad, hyper=(lr, 1 - b1 ** self._adam_step, 1 - b2 ** self._adam_step))
         self.last_lr = lr
 
     def set_hyper(self, lr, bc1, bc2):
@@ -499,16 +518,16 @@ class ScheduledOptim:
         ev.record()
         self._hyper_ev[i] = ev
 
-    def apply_update(self, zero_grad=False):
-        """The capturable part: ||g||^2, then clip+Adam over the flat buffers (reads lr / bias corrections from device).
+    def apply_update(self, zero_grad=False, hyper=None):
+        """The capturable part: ||g||^2, then clip+Adam over the flat buffers (reads lr / bias corrections from device, as
+        set_hyper left them, unless `hyper` = (lr, 1 - b1^t, 1 - b2^t) hands them over as launch arguments).
         The same pass refreshes the bf16 shadow parameters the forward GEMMs read and (optionally) clears the gradients."""
         b1, b2 = self.betas
         g = self.model.flat_gradients()
-        self._nsq.zero_()
-        ops.sumsq(g, self._nsq, self._nsq_ws)
+        ops.sumsq(g, self._nsq, self._nsq_ws, set=True)     # (stores the norm: no clear of _nsq in front)
         lowp = self.model._engine.lowp_buffer() if self.model._engine is not None else None
-        ops.adam_step(self.model.flat_parameters(), g, self._m, self._v, self._nsq, self.grad_clip_thresh, self._hyper,
-                      b1, b2, self.eps, self.weight_decay, p_lowp=lowp, zero_grad=zero_grad)
+        ops.adam_step(self.model.flat_parameters(), g, self._m, self._v, self._nsq, self.grad_clip_thresh,
+                      self._hyper if hyper is None else hyper, b1, b2, self.eps, self.weight_decay, p_lowp=lowp, zero_grad=zero_grad)
         self.model._invalidate(lowp_synced=lowp is not None)
 
     def zero_grad(self):

@@ -340,9 +340,23 @@ def ln_bwd_reduce(ws, C, dgamma, dbeta):
 
 
 # ------------------------------------------------------------------ batch norm
+def bn_apply_out32(x, mean_rstd, gamma, beta, res, act, p, seed, seed_dev=None, want_out=False, want_res32=True):
+    """BatchNorm apply whose result leaves as fp32 (fs2_bn_apply_out32): -> (out or None, out32, res32 or None).  out32 / res32 hold
+    exactly what cast(out, float32) / cast(res, float32) would."""
+    M, C = x.shape
+    out = torch.empty_like(x) if want_out else None
+    out32 = torch.empty(M, C, device=x.device, dtype=torch.float32)
+    res32 = torch.empty(M, C, device=x.device, dtype=torch.float32) if (want_res32 and res is not None) else None
+    _lib.call("fs2_bn_apply_out32", _p(x), _p(mean_rstd), _p(gamma), _p(beta), _p(res), _p(out), _p(out32), _p(res32), M, C, act, p, seed,
+              _p(seed_dev), dt(x), _stream())
+    return out, out32, res32
+
+
 def bn_train_fwd(x, gamma, beta, running_mean, running_var, act, p, seed, eps=1e-5, momentum=0.1, res=None, seed_dev=None,
-                 ws=None, num_batches_tracked=None):
-    """ws: a persistent BN workspace (bn_workspace(C), reused by every call of width C: each call writes every slab word it reads): statistics, running-stat
+                 ws=None, num_batches_tracked=None, out32=False):
+    """out32=True: the result (and the residual operand) leave as fp32 images, no compute-dtype result is stored: returns
+    ((out32, res32), mean_rstd).
+    ws: a persistent BN workspace (bn_workspace(C), reused by every call of width C: each call writes every slab word it reads): statistics, running-stat
     update and the num_batches_tracked increment then take two launches, with no fill / fix-up / counter launches around them."""
     M, C = x.shape
     mean_rstd = torch.empty(2 * C, device=x.device, dtype=torch.float32)
@@ -354,6 +368,9 @@ def bn_train_fwd(x, gamma, beta, running_mean, running_var, act, p, seed, eps=1e
         _lib.call("fs2_bn_stats", _p(x), _p(stats), stats.numel(), M, C, dt(x), _stream())
         _lib.call("fs2_bn_finalize", _p(stats), _p(running_mean), _p(running_var), _p(mean_rstd), M, C, eps, momentum,
                   _stream())
+    if out32:
+        _, o32, r32 = bn_apply_out32(x, mean_rstd, gamma, beta, res, act, p, seed, seed_dev=seed_dev)
+        return (o32, r32), mean_rstd
     out = torch.empty_like(x)
     _lib.call("fs2_bn_apply", _p(x), _p(mean_rstd), _p(gamma), _p(beta), _p(res), _p(out), M, C, act, p, seed, _p(seed_dev),
               dt(x), _stream())
@@ -448,6 +465,17 @@ def lr_gather_bwd(dy, cum, B, L, T, dx=None, accumulate=False):
     return dx
 
 
+def lr_gather_bwd_add(dy, cum, add1, add2, B, L, T):
+    """lr_gather_bwd and the adds behind it in one launch: -> (dx0, dx0 + add1, (dx0 + add1) + add2 or None), every stage stored
+    (and rounded) in dy's dtype exactly as lr_gather_bwd + add + add store them."""
+    C = dy.shape[-1]
+    dx0 = torch.empty(B * L, C, device=dy.device, dtype=dy.dtype)
+    dx1 = torch.empty_like(dx0)
+    dx2 = torch.empty_like(dx0) if add2 is not None else None
+    _lib.call("fs2_lr_gather_bwd_add", _p(dy), _p(cum), _p(_contig(add1)), _p(add2), _p(dx0), _p(dx1), _p(dx2), B, L, T, C, dt(dy), _stream())
+    return dx0, dx1, dx2
+
+
 def duration_round(logd, d_control):
     out = torch.empty_like(logd)
     _lib.call("fs2_duration_round", _p(logd), float(d_control), _p(out), logd.numel(), _stream())
@@ -480,15 +508,21 @@ def cast(x, dtype, out=None):
 
 
 # ------------------------------------------------------------------ optimiser
-def sumsq(x, out, ws=None):
-    """out[0] += ||x||^2, bit-reproducible (fixed summation order).  ws: >= 1024 floats of workspace."""
+def sumsq(x, out, ws=None, set=False):
+    """out[0] += ||x||^2 (set=True: out[0] = ||x||^2, nothing to clear first), bit-reproducible (fixed summation order).
+    ws: >= 1024 floats of workspace."""
     if ws is None:
         ws = torch.empty(1024, device=x.device, dtype=torch.float32)
-    _lib.call("fs2_sumsq", _p(x), x.numel(), _p(out), _p(ws), _stream())
+    _lib.call("fs2_sumsq_set" if set else "fs2_sumsq", _p(x), x.numel(), _p(out), _p(ws), _stream())
 
 
 def adam_step(p, g, m, v, gnorm_sq, max_norm, hyper, b1, b2, eps, wd, p_lowp=None, zero_grad=False):
-    """clip + Adam over the flat buffers; optionally writes the bf16 shadow copy of p and clears g in the same pass."""
+    """clip + Adam over the flat buffers; optionally writes the bf16 shadow copy of p and clears g in the same pass.
+    hyper: the device vector [lr, 1 - b1^t, 1 - b2^t, .], or a host (lr, 1 - b1^t, 1 - b2^t) tuple passed as launch arguments."""
+    if isinstance(hyper, tuple):
+        _lib.call("fs2_adam_step_h", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(gnorm_sq), float(max_norm), hyper[0], hyper[1], hyper[2],
+                  b1, b2, eps, wd, _p(p_lowp), BF16 if p_lowp is not None else 0, int(zero_grad), _stream())
+        return
     _lib.call("fs2_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(gnorm_sq), float(max_norm), _p(hyper), b1, b2,
               eps, wd, _p(p_lowp), BF16 if p_lowp is not None else 0, int(zero_grad), _stream())
 
@@ -514,13 +548,32 @@ def bump_counter(ctr, inc=1):
 
 
 # ------------------------------------------------------------------ loss
+_loss_ws = {}
+
+
+def _loss_workspace(device):
+    """the loss forward's partial sums (fs2_loss_fwd_ws): zeroed once here, left zero by every forward.  One per (device, stream):
+    forwards that share one are ordered by their stream.  Not made inside a hipGraph capture (its zero fill would be replayed in
+    the graph's private pool, not here): a capture takes the self-clearing entry point."""
+    key = (device.index, _stream())
+    ws = _loss_ws.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        ws = _loss_ws[key] = torch.zeros(8, device=device, dtype=torch.float32)
+    return ws
+
+
 def loss_fwd(mel, post, mel_t, mel_lens, src_lens, p_pred, p_t, e_pred, e_t, logd, dur, cnt, p_frame, e_frame):
     """-> losses[6] (device f32): total, mel, postnet, pitch, energy, duration."""
     B, T, n_mel = mel.shape
     L = logd.shape[1]
-    sums = torch.empty(5, device=mel.device, dtype=torch.float32)
     losses = torch.empty(6, device=mel.device, dtype=torch.float32)
-    _lib.call("fs2_loss_fwd", _p(mel), _p(post), _p(mel_t), mel_t.stride(0), _p(mel_lens), _p(src_lens), _p(p_pred), _p(p_t),
+    sums = _loss_workspace(mel.device)
+    entry = "fs2_loss_fwd_ws"
+    if sums is None:
+        entry, sums = "fs2_loss_fwd", torch.empty(5, device=mel.device, dtype=torch.float32)
+    _lib.call(entry, _p(mel), _p(post), _p(mel_t), mel_t.stride(0), _p(mel_lens), _p(src_lens), _p(p_pred), _p(p_t),
               p_t.stride(0), _p(e_pred), _p(e_t), e_t.stride(0), _p(logd), _p(dur), dur.stride(0), _p(cnt), B, T, L, n_mel,
               int(p_frame), int(e_frame), _p(sums), _p(losses), _stream())
     return losses
@@ -534,4 +587,18 @@ def loss_bwd(mel, post, mel_t, mel_lens, src_lens, p_pred, p_t, e_pred, e_t, log
     _lib.call("fs2_loss_bwd", _p(mel), _p(post), _p(mel_t), mel_t.stride(0), _p(mel_lens), _p(src_lens), _p(p_pred), _p(p_t),
               p_t.stride(0), _p(e_pred), _p(e_t), e_t.stride(0), _p(logd), _p(dur), dur.stride(0), _p(cnt), _p(g), B, T, L, n_mel,
               int(p_frame), int(e_frame), _p(dmel), _p(dpost), _p(dp), _p(de), _p(dlogd), _stream())
+    return dmel, dpost, dp, de, dlogd
+
+
+def loss_bwd_lp(mel, post, mel_t, mel_lens, src_lens, p_pred, p_t, e_pred, e_t, logd, dur, cnt, gs, p_frame, e_frame, grad_dtype):
+    """loss_bwd with the upstream factors as six 0-dim device tensors (gs; None = that term was not differentiated) and dmel / dpost
+    stored in grad_dtype as rows [B*T, n_mel] (bf16: the fp32 gradient rounded as `cast` rounds it)."""
+    B, T, n_mel = mel.shape
+    L = logd.shape[1]
+    dmel = torch.empty(B * T, n_mel, device=mel.device, dtype=grad_dtype)
+    dpost = torch.empty(B * T, n_mel, device=mel.device, dtype=grad_dtype)
+    dp, de, dlogd = torch.empty_like(p_pred), torch.empty_like(e_pred), torch.empty_like(logd)
+    _lib.call("fs2_loss_bwd_lp", _p(mel), _p(post), _p(mel_t), mel_t.stride(0), _p(mel_lens), _p(src_lens), _p(p_pred), _p(p_t),
+              p_t.stride(0), _p(e_pred), _p(e_t), e_t.stride(0), _p(logd), _p(dur), dur.stride(0), _p(cnt), *[_p(g) for g in gs], B, T, L,
+              n_mel, int(p_frame), int(e_frame), _p(dmel), _p(dpost), dt(grad_dtype), _p(dp), _p(de), _p(dlogd), _stream())
     return dmel, dpost, dp, de, dlogd

@@ -199,6 +199,11 @@ int fs2_bn_finalize(const float* stats, float* running_mean, float* running_var,
  * hipGraph draws a fresh mask each step. */
 int fs2_bn_apply(const void* x, const float* mean_rstd, const float* gamma, const float* beta, const void* res, void* out,
                  int M, int C, int act, float p, uint64_t seed, const uint64_t* seed_dev, int dtype, fs2_stream_t stream);
+/* fs2_bn_apply that also writes fp32 images: out32 [M][C] = the result as stored in `dtype`, widened (bit for bit what fs2_cast
+ * makes of `out`); res32 (optional, needs res) = the residual operand widened.  out may be NULL (only the fp32 image wanted). */
+int fs2_bn_apply_out32(const void* x, const float* mean_rstd, const float* gamma, const float* beta, const void* res, void* out,
+                       float* out32, float* res32, int M, int C, int act, float p, uint64_t seed, const uint64_t* seed_dev,
+                       int dtype, fs2_stream_t stream);
 int fs2_bn_bwd(const void* x, const void* dout, const float* mean_rstd, const float* gamma, const float* beta,
                float* sums /*workspace; [0,2C) = dbeta|dgamma*/, long ws_floats, void* dx, int M, int C, int act, float p,
                uint64_t seed, const uint64_t* seed_dev, int dtype, fs2_stream_t stream);
@@ -237,6 +242,10 @@ int fs2_lr_gather_fwd(const void* x, const int32_t* idx, const float* pe, void* 
                       int dtype, fs2_stream_t stream);
 int fs2_lr_gather_bwd(const void* dy, const int32_t* cum, void* dx, int B, int L, int T, int C, int accumulate,
                       int dtype, fs2_stream_t stream);
+/* fs2_lr_gather_bwd and the residual adds behind it in one launch: dx0 = segment sums, dx1 = dx0 + add1, dx2 = dx1 + add2
+ * (add2 / dx2 optional), every stage rounded to `dtype` before the next add - bit for bit fs2_lr_gather_bwd + fs2_add + fs2_add. */
+int fs2_lr_gather_bwd_add(const void* dy, const int32_t* cum, const void* add1, const void* add2, void* dx0, void* dx1, void* dx2,
+                          int B, int L, int T, int C, int dtype, fs2_stream_t stream);
 /* model/modules.py:132-135: clamp(round_half_even(exp(log_d)-1) * d_control, min=0) */
 int fs2_duration_round(const float* logd, float d_control, float* out, int n, fs2_stream_t stream);
 /* model/modules.py:243-249: out[r] = mask(dot(x[r,:], w) + b) */
@@ -422,17 +431,36 @@ int fs2_loss_bwd(const float* mel, const float* post, const float* mel_t, long l
                  const float* e_t, long ld_et, const float* logd, const int64_t* dur, long ld_dur, const float* cnt,
                  const float* g, int B, int T, int L, int n_mel, int p_frame, int e_frame, float* dmel, float* dpost,
                  float* dp, float* de, float* dlogd, fs2_stream_t stream);
+/* fs2_loss_fwd with a KEPT workspace: sums_ws (5 floats) is zero on entry (zeroed once by its owner) and zero again on return,
+ * so no clear is launched in front; calls sharing one workspace must be ordered. */
+int fs2_loss_fwd_ws(const float* mel, const float* post, const float* mel_t, long ld_t_b, const int64_t* mel_lens,
+                    const int64_t* src_lens, const float* p_pred, const float* p_t, long ld_pt, const float* e_pred,
+                    const float* e_t, long ld_et, const float* logd, const int64_t* dur, long ld_dur, const float* cnt,
+                    int B, int T, int L, int n_mel, int p_frame, int e_frame, float* sums_ws, float* losses, fs2_stream_t stream);
+/* fs2_loss_bwd with the upstream factors as six device scalars (NULL = 0: that term was not differentiated) and dmel / dpost
+ * stored in grad_dtype (FS2_BF16: rounded to nearest even, bit for bit fs2_cast of the fp32 gradient), rows [B*T][n_mel]. */
+int fs2_loss_bwd_lp(const float* mel, const float* post, const float* mel_t, long ld_t_b, const int64_t* mel_lens,
+                    const int64_t* src_lens, const float* p_pred, const float* p_t, long ld_pt, const float* e_pred,
+                    const float* e_t, long ld_et, const float* logd, const int64_t* dur, long ld_dur, const float* cnt,
+                    const float* g_total, const float* g_mel, const float* g_post, const float* g_pitch, const float* g_energy,
+                    const float* g_dur, int B, int T, int L, int n_mel, int p_frame, int e_frame, void* dmel, void* dpost,
+                    int grad_dtype, float* dp, float* de, float* dlogd, fs2_stream_t stream);
 
 /* ---- optimiser: train.py:93 clip_grad_norm_ + model/optimizer.py:10-51 Adam ------------------------- */
 /* ws: FS2_SUMSQ_BLOCKS floats of workspace (two-stage reduction in a fixed order: bit-reproducible norm) */
 #define FS2_SUMSQ_BLOCKS 1024
 int fs2_sumsq(const float* x, size_t n, float* out /*+=*/, float* ws, fs2_stream_t stream);
+int fs2_sumsq_set(const float* x, size_t n, float* out /*=: no clear needed in front*/, float* ws, fs2_stream_t stream);
 /* hyper (device) = {lr, 1-beta1^t, 1-beta2^t}; clip = min(1, max_norm/(sqrt(*gnorm_sq)+1e-6)).
  * p_lowp (optional, bf16): compute-dtype copy of the updated parameters written in the same pass;
  * zero_grad: clear g as it is consumed (optimizer.zero_grad(), model/optimizer.py:30-31).  n % 4 == 0. */
 int fs2_adam_step(float* p, float* g, float* m, float* v, size_t n, const float* gnorm_sq, float max_norm,
                   const float* hyper, float b1, float b2, float eps, float wd, void* p_lowp, int lowp_dtype, int zero_grad,
                   fs2_stream_t stream);
+/* the same with lr / 1-beta1^t / 1-beta2^t as launch arguments (eager steps: no host-to-device copy in front of the optimiser) */
+int fs2_adam_step_h(float* p, float* g, float* m, float* v, size_t n, const float* gnorm_sq, float max_norm, float lr, float bc1,
+                    float bc2, float b1, float b2, float eps, float wd, void* p_lowp, int lowp_dtype, int zero_grad,
+                    fs2_stream_t stream);
 
 #ifdef __cplusplus
 }
