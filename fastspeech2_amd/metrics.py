@@ -1,0 +1,404 @@
+"""Objective scoring of synthesized against recorded speech on the GPU: mel-cepstral distortion (MCD) along a dynamic-time-warping
+(DTW) path, and F0 RMSE and voiced / unvoiced (V/UV) error on the same path.  HIP kernels in fp64 over ragged batches of pairs
+(csrc/fs2_dtw.hip).  The specification below is what the kernels and the numpy oracle (tests/dtw_ref.py) implement.
+
+WHAT THE NUMBERS ARE.  The cepstra are a DCT of this project's own 80-band natural-log mel spectrogram (`audio.TacotronSTFT`), not
+WORLD / SPTK mel-cepstra of a spectral envelope.  The dB values compare two runs of this tool with each other; they are not
+comparable with MCD figures published elsewhere.
+
+Cepstra.  x[m][t] is the log-mel (B, n_mel, T) exactly as `TacotronSTFT.mel_spectrogram_ragged` returns it, with its frame counts.
+c[k][t] = sum_m x[m][t] C[k][m], m ascending, with the orthonormal DCT-II rows C[k][m] = sqrt(2 / n_mel) cos(pi k (2 m + 1) / (2 n_mel)),
+k = 1 .. K (c0, the level, is excluded).  K = n_mcep defaults to 13 and is at most 40; n_mel is at most 128.  C is built on the host
+in numpy float64 (`dct_table`) and uploaded: the device evaluates no cosine.  All arithmetic from here on is float64.
+
+DTW, per pair (a: T1 reference frames, index i; b: T2 synthesized frames, index j).
+  local cost    d(i, j) = sqrt(sum_k (a_k[i] - b_k[j])^2), k ascending, the products not fused into the sum, the root correctly rounded
+  accumulated   D(0, 0) = d(0, 0);  D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), a missing neighbour = +inf
+  backpointer   0 = (i-1, j-1), 1 = (i-1, j), 2 = (i, j-1); the lowest code wins ties (the aligner's rule); (0, 0) has code 0
+  path          from (0, 0) to (T1-1, T2-1), P cells, max(T1, T2) <= P <= T1 + T2 - 1
+There is no band (no Sakoe-Chiba window) and there are no slope weights.  1 <= T1, T2 <= 2048 (`max_frames()`); a longer sequence is
+a ValueError before any launch.
+
+Scores per pair.  mcd_db = (10 / ln 10) sqrt(2) D(T1-1, T2-1) / P.  With r = f0_ref[i], s = f0_syn[j] over the P path cells (i, j):
+vuv_error = the share of cells where exactly one of r, s is 0;  f0_rmse_cents = sqrt(mean over the cells with r > 0 and s > 0 of
+(1200 log2(s / r))^2), NaN when there is no such cell; n_voiced_pairs is their number.  Also path_len = P, frames_ref = T1,
+frames_syn = T2.  F0 is DIO + StoneMask (`pitch`) with frame_period = hop / sampling_rate * 1000 as in `Preprocessor._extract_pitch`,
+on the unclamped audio; the mel is taken of the audio clamped to [-1, 1].  F0 frame f and mel frame f are both centred at sample
+f * hop.  Where the two frame counts of an utterance differ (the last frame), both are cut to the smaller before the DTW.
+
+Corpus summary (`summarize`).  For mcd_db, f0_rmse_cents and vuv_error the mean of the per-utterance values and the mean weighted by
+path_len (F0: over the utterances whose value is not NaN, weighted by n_voiced_pairs), and the number of utterances whose F0 score
+is NaN.
+
+Storage.  The local costs and backpointers of a pair are held skewed, cell (i, j) at row (i + j) mod T2, column i of a (T2max, T1max)
+matrix: an anti-diagonal is contiguous, the buffer is no larger than the plain one (`unskew` undoes it for a test).  The accumulated
+costs never leave the chip.  Determinism: no atomics, sums in a fixed order; two runs give byte-identical scores.
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, ops, ragged
+
+WHO = "fastspeech2_amd.metrics"
+MAX_FRAMES, MAX_MCEP, MAX_MEL = 2048, 40, 128
+MCD_SCALE = 10.0 / math.log(10.0) * math.sqrt(2.0)
+CELL_BYTES = 9                                              # one float64 local cost and one backpointer byte per (i, j)
+
+
+def max_frames():
+    return _lib.load().fs2_dtw_max_frames()
+
+
+def dct_table(n_mel, n_mcep=13):
+    """C (n_mcep, n_mel) float64: rows k = 1 .. n_mcep of the orthonormal DCT-II."""
+    if not 1 <= n_mcep <= MAX_MCEP or not 1 <= n_mel <= MAX_MEL or n_mcep >= n_mel:
+        raise ValueError(f"n_mcep must be in [1, {MAX_MCEP}] and below n_mel <= {MAX_MEL}, got n_mcep={n_mcep}, n_mel={n_mel}")
+    k = np.arange(1, n_mcep + 1, dtype=np.float64)[:, None]
+    m = np.arange(n_mel, dtype=np.float64)[None, :]
+    return np.sqrt(2.0 / n_mel) * np.cos(np.pi * k * (2.0 * m + 1.0) / (2.0 * n_mel))
+
+
+def check_frames(*lens):
+    """Every length in [1, MAX_FRAMES], else ValueError: called before anything touches the device."""
+    for ls in lens:
+        for n in ls:
+            if not 1 <= int(n) <= MAX_FRAMES:
+                raise ValueError(f"a sequence of {int(n)} frames is outside the supported 1..{MAX_FRAMES} frames")
+
+
+def _host_lens(lens):
+    return [int(v) for v in (lens.tolist() if isinstance(lens, (torch.Tensor, np.ndarray)) else lens)]
+
+
+def _dev(t, dtype, what, dim):
+    ragged.require_device(t, WHO)
+    if t.dtype != dtype or t.dim() != dim or (t.numel() and t.stride(-1) != 1):
+        raise ValueError(f"{what} must be a {dim}-D {dtype} tensor with unit inner stride, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _out(out, shape, dtype, what, device):
+    """A caller's output buffer (any batch / row strides, at least `shape`) or a fresh one."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    out = _dev(out, dtype, what, len(shape))
+    if out.shape[0] != shape[0] or any(o < s for o, s in zip(out.shape[1:], shape[1:])):
+        raise ValueError(f"{what} {tuple(out.shape)} is too small for {tuple(shape)}")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ kernels
+_tables = {}
+
+
+def cepstra(mel, lens, n_mcep=13, out=None):
+    """mel (B, n_mel, frames) float32 log-mel on the device, lens frames per row -> c (B, Tmax, n_mcep) float64."""
+    ragged.require_device(mel, WHO)
+    if mel.dtype != torch.float32 or mel.dim() != 3 or (mel.numel() and mel.stride(2) != 1):
+        raise ValueError(f"mel must be a (B, n_mel, frames) float32 tensor with unit inner stride, got {mel.dtype} {tuple(mel.shape)}")
+    B, n_mel, F = mel.shape
+    lens_h, lens_d = ragged.lengths(lens, B, F, "lens", mel.device)
+    key = (str(mel.device), n_mel, n_mcep)
+    if key not in _tables:
+        _tables[key] = torch.from_numpy(dct_table(n_mel, n_mcep)).to(mel.device)
+    Tmax = max(lens_h, default=0)
+    c = _out(out, (B, Tmax, n_mcep), torch.float64, "out", mel.device)
+    _lib.call("fs2_mcep", mel.data_ptr(), mel.stride(0), mel.stride(1), lens_d.data_ptr(), _tables[key].data_ptr(), n_mcep,
+              c.data_ptr(), c.stride(0), c.stride(1), B, n_mel, Tmax, ops._stream())
+    return c
+
+
+def _pairs(a, alens, b, blens):
+    ah, bh = _host_lens(alens), _host_lens(blens)
+    check_frames(ah, bh)
+    a, b = _dev(a, torch.float64, "a", 3), _dev(b, torch.float64, "b", 3)
+    B, K = a.shape[0], a.shape[2]
+    if b.shape[0] != B or b.shape[2] != K or not 1 <= K <= MAX_MCEP:
+        raise ValueError(f"a {tuple(a.shape)} and b {tuple(b.shape)} are not B pairs of up to {MAX_MCEP} coefficients")
+    _, ad = ragged.lengths(ah, B, a.shape[1], "alens", a.device)
+    _, bd = ragged.lengths(bh, B, b.shape[1], "blens", a.device)
+    return a, b, ah, bh, ad, bd, B, K
+
+
+def _pair_lens(alens, blens):
+    """Host lengths of both sides, refused before the device is touched when one is outside 1..MAX_FRAMES."""
+    ah, bh = _host_lens(alens), _host_lens(blens)
+    check_frames(ah, bh)
+    return ah, bh, max(ah, default=0), max(bh, default=0)
+
+
+def _lens_dev(ah, bh, B, device):
+    return ragged.lengths(ah, B, MAX_FRAMES, "alens", device)[1], ragged.lengths(bh, B, MAX_FRAMES, "blens", device)[1]
+
+
+def local_cost(a, alens, b, blens, out=None):
+    """a (B, >= T1max, K), b (B, >= T2max, K) float64 cepstra -> the skewed local costs (B, T2max, T1max) float64."""
+    a, b, ah, bh, ad, bd, B, K = _pairs(a, alens, b, blens)
+    T1, T2 = max(ah, default=0), max(bh, default=0)
+    cost = _out(out, (B, T2, T1), torch.float64, "out", a.device)
+    _lib.call("fs2_dtw_cost", a.data_ptr(), a.stride(0), a.stride(1), ad.data_ptr(), b.data_ptr(), b.stride(0), b.stride(1),
+              bd.data_ptr(), K, cost.data_ptr(), cost.stride(0), cost.stride(1), B, T1, T2, ops._stream())
+    return cost
+
+
+def scan(cost, alens, blens, out=None):
+    """skewed local costs (B, >= T2max, >= T1max) -> (skewed backpointers uint8 (B, T2max, T1max), total (B,) float64)."""
+    ah, bh, T1, T2 = _pair_lens(alens, blens)
+    cost = _dev(cost, torch.float64, "cost", 3)
+    B = cost.shape[0]
+    ad, bd = _lens_dev(ah, bh, B, cost.device)
+    if cost.shape[1] < T2 or cost.shape[2] < T1:
+        raise ValueError(f"cost {tuple(cost.shape)} does not hold pairs of up to {T1} x {T2} frames")
+    bp = _out(out, (B, T2, T1), torch.uint8, "out", cost.device)
+    total = torch.empty(B, dtype=torch.float64, device=cost.device)
+    _lib.call("fs2_dtw_scan", cost.data_ptr(), cost.stride(0), cost.stride(1), ad.data_ptr(), bd.data_ptr(), bp.data_ptr(),
+              bp.stride(0), bp.stride(1), total.data_ptr(), B, T1, T2, ops._stream())
+    return bp, total
+
+
+def backtrack(bp, alens, blens, out=None):
+    """skewed backpointers -> (path_len (B,) int32, pi, pj (B, T1max + T2max - 1) int32): the path from (0, 0); entries beyond a
+    pair's path_len and below its T1 + T2 - 1 are -1.  `out` = (pi, pj) buffers of the caller."""
+    ah, bh, T1, T2 = _pair_lens(alens, blens)
+    bp = _dev(bp, torch.uint8, "bp", 3)
+    B = bp.shape[0]
+    ad, bd = _lens_dev(ah, bh, B, bp.device)
+    if bp.shape[1] < T2 or bp.shape[2] < T1:
+        raise ValueError(f"bp {tuple(bp.shape)} does not hold pairs of up to {T1} x {T2} frames")
+    L = max(T1 + T2 - 1, 1)
+    pi = _out(None if out is None else out[0], (B, L), torch.int32, "out[0]", bp.device)
+    pj = _out(None if out is None else out[1], (B, L), torch.int32, "out[1]", bp.device)
+    if pi.stride(0) != pj.stride(0):
+        raise ValueError("the two path buffers need the same row stride")
+    plen = torch.empty(B, dtype=torch.int32, device=bp.device)
+    _lib.call("fs2_dtw_backtrack", bp.data_ptr(), bp.stride(0), bp.stride(1), ad.data_ptr(), bd.data_ptr(), pi.data_ptr(),
+              pj.data_ptr(), pi.stride(0), plen.data_ptr(), B, T1, T2, ops._stream())
+    return plen, pi, pj
+
+
+def dtw(a, alens, b, blens):
+    """Cepstra a (B, T1max, K), b (B, T2max, K) float64 on the device -> (total (B,) float64 = D(T1-1, T2-1), path_len (B,) int32,
+    pi, pj (B, T1max + T2max - 1) int32), all on the device."""
+    cost = local_cost(a, alens, b, blens)
+    bp, total = scan(cost, alens, blens)
+    del cost
+    plen, pi, pj = backtrack(bp, alens, blens)
+    return total, plen, pi, pj
+
+
+def f0_on_path(pi, pj, path_len, f0_ref, alens, f0_syn, blens, out=None):
+    """Path (pi, pj, path_len as `dtw` returns them) and F0 tracks f0_ref (B, >= T1max), f0_syn (B, >= T2max) float64 on the device
+    -> sums (B, 3) float64: V/UV mismatches, both-voiced cells, the sum of their squared cents."""
+    ah, bh, T1, T2 = _pair_lens(alens, blens)
+    pi, pj = _dev(pi, torch.int32, "pi", 2), _dev(pj, torch.int32, "pj", 2)
+    B = pi.shape[0]
+    ad, bd = _lens_dev(ah, bh, B, pi.device)
+    f0_ref, f0_syn = _dev(f0_ref, torch.float64, "f0_ref", 2), _dev(f0_syn, torch.float64, "f0_syn", 2)
+    path_len = _dev(path_len, torch.int32, "path_len", 1)
+    if pj.shape != pi.shape or pi.stride(0) != pj.stride(0) or path_len.shape[0] != B or f0_ref.shape[0] != B or f0_syn.shape[0] != B \
+            or f0_ref.shape[1] < T1 or f0_syn.shape[1] < T2:
+        raise ValueError(f"path {tuple(pi.shape)} {tuple(pj.shape)}, f0 {tuple(f0_ref.shape)} {tuple(f0_syn.shape)} and the lengths "
+                         f"do not fit together")
+    sums = _out(out, (B, 3), torch.float64, "out", pi.device)
+    _lib.call("fs2_dtw_f0", pi.data_ptr(), pj.data_ptr(), pi.stride(0), path_len.data_ptr(), f0_ref.data_ptr(), f0_ref.stride(0),
+              f0_syn.data_ptr(), f0_syn.stride(0), ad.data_ptr(), bd.data_ptr(), sums.data_ptr(), sums.stride(0), B, T1, T2,
+              ops._stream())
+    return sums
+
+
+def unskew(m, alens, blens, fill):
+    """Skewed (B, T2max, T1max) numpy array -> plain (B, T1max, T2max) with `fill` outside each pair (for tests and debugging)."""
+    m = np.asarray(m)
+    out = np.full((m.shape[0], m.shape[2], m.shape[1]), fill, m.dtype)
+    for p, (T1, T2) in enumerate(zip(alens, blens)):
+        i, j = np.meshgrid(np.arange(T1), np.arange(T2), indexing="ij")
+        out[p, :T1, :T2] = m[p, (i + j) % T2, i]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ scores
+def scores_from_sums(total, path_len, frames_ref, frames_syn, sums=None):
+    """The per-pair dict of the module docstring from the device results copied to the host."""
+    P = int(path_len)
+    row = {"mcd_db": MCD_SCALE * float(total) / P, "path_len": P, "frames_ref": int(frames_ref), "frames_syn": int(frames_syn)}
+    if sums is not None:
+        nv = int(sums[1])
+        row["vuv_error"] = float(sums[0]) / P
+        row["f0_rmse_cents"] = math.sqrt(float(sums[2]) / nv) if nv else float("nan")
+        row["n_voiced_pairs"] = nv
+    return row
+
+
+def summarize(rows):
+    """Corpus summary of per-utterance score dicts (module docstring)."""
+    out = {"utterances": len(rows)}
+    if not rows:
+        return out
+    w = np.array([r["path_len"] for r in rows], np.float64)
+    mcd = np.array([r["mcd_db"] for r in rows], np.float64)
+    out["mcd_db_mean"] = float(mcd.mean())
+    out["mcd_db_weighted"] = float((mcd * w).sum() / w.sum())
+    if "vuv_error" in rows[0]:
+        vuv = np.array([r["vuv_error"] for r in rows], np.float64)
+        f0 = np.array([r["f0_rmse_cents"] for r in rows], np.float64)
+        nv = np.array([r["n_voiced_pairs"] for r in rows], np.float64)
+        ok = ~np.isnan(f0)
+        out["vuv_error_mean"] = float(vuv.mean())
+        out["vuv_error_weighted"] = float((vuv * w).sum() / w.sum())
+        out["f0_rmse_cents_mean"] = float(f0[ok].mean()) if ok.any() else float("nan")
+        out["f0_rmse_cents_weighted"] = float((f0[ok] * nv[ok]).sum() / nv[ok].sum()) if ok.any() else float("nan")
+        out["f0_nan_utterances"] = int((~ok).sum())
+    return out
+
+
+def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256):
+    """What a batch of n pairs padded to (T1, T2) frames holds on the device: 9 B per (i, j) cell (local cost + backpointer), the
+    audio, its STFT workspace and mel (about 40 B per sample), cepstra, F0 and the path."""
+    return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64))
+
+
+def load_audio(path, sampling_rate):
+    """float32 mono waveform of a wav file that must already be at `sampling_rate`."""
+    from .preprocess import load_wav
+    wav, sr = load_wav(path, resample=False)
+    if sr != sampling_rate:
+        raise ValueError(f"{path} is at {sr} Hz, the config's sampling_rate is {sampling_rate} Hz: scoring does not resample; convert "
+                         f"the corpus with prepare_align.py (its --resample gpu path) first")
+    return wav.astype(np.float32)
+
+
+def frame_counts(n_samples, sampling_rate, hop_length, f0=True):
+    """Frames of an utterance of n samples: the mel's n // hop + 1, cut to DIO's count where that is smaller."""
+    from .pitch import frame_count
+    T = n_samples // hop_length + 1
+    return min(T, frame_count(n_samples, sampling_rate, hop_length / sampling_rate * 1000)) if f0 else T
+
+
+def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=13, f0=True, device="cuda", budget=4 << 30):
+    """Scores of (recorded, synthesized) pairs of float32 waveforms at `sampling_rate` -> one dict per pair (module docstring), in
+    the order given.  `stft` is the config's `audio.TacotronSTFT`.  Pairs are packed longest first into ragged batches under `budget`
+    bytes of device buffers; per batch: both sides through one pinned staging buffer, mel -> cepstra -> local cost -> scan ->
+    backtrack (and DIO + StoneMask -> the path sums with `f0`), one D2H copy of the scores."""
+    if len(ref_wavs) != len(syn_wavs):
+        raise ValueError(f"{len(ref_wavs)} reference and {len(syn_wavs)} synthesized waveforms")
+    if hop_length != stft.hop_length:
+        raise ValueError(f"hop_length {hop_length} is not the STFT's {stft.hop_length}")
+    dct_table(stft.n_mel_channels, n_mcep)                                  # validates n_mcep before any work
+    fr = [frame_counts(len(w), sampling_rate, hop_length, f0) for w in ref_wavs]
+    fs = [frame_counts(len(w), sampling_rate, hop_length, f0) for w in syn_wavs]
+    check_frames(fr, fs)
+    short = [len(w) for w in list(ref_wavs) + list(syn_wavs) if len(w) <= stft.filter_length // 2]
+    if short:
+        raise ValueError(f"a waveform of {short[0]} samples is too short for the STFT's reflect padding ({stft.filter_length // 2})")
+    dev = ragged.require_device(torch.device(device), WHO)
+    staging = ragged.Staging()
+    frame_period = hop_length / sampling_rate * 1000
+    rows = [None] * len(ref_wavs)
+
+    def side(wavs, frames):
+        staging.pack(wavs)
+        y, lens = staging.to(dev), [len(w) for w in wavs]
+        mel, _, _ = stft.mel_spectrogram_ragged(y.clamp(-1.0, 1.0), lens)
+        c = cepstra(mel, frames, n_mcep)
+        if not f0:
+            return c, None
+        from . import pitch as Pitch
+        f, _, f_frames = Pitch.dio(y, lens, sampling_rate, frame_period)
+        return c, Pitch.stonemask(y, lens, f, f_frames, sampling_rate, frame_period)
+
+    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length)     # noqa: E731
+    for batch in ragged.greedy_batches(list(zip(fr, fs)), budget, cost):
+        al, bl = [fr[i] for i in batch], [fs[i] for i in batch]
+        a, f0a = side([ref_wavs[i] for i in batch], al)
+        b, f0b = side([syn_wavs[i] for i in batch], bl)
+        total, plen, pi, pj = dtw(a, al, b, bl)
+        cols = [total, plen.to(torch.float64)]
+        if f0:
+            cols += list(f0_on_path(pi, pj, plen, f0a, al, f0b, bl).unbind(1))
+        host = torch.stack(cols, dim=1).cpu().numpy()                       # the batch's one D2H copy
+        for r, i in enumerate(batch):
+            rows[i] = scores_from_sums(host[r, 0], host[r, 1], al[r], bl[r], host[r, 2:5] if f0 else None)
+    return rows
+
+
+# ------------------------------------------------------------------------------------------------ the corpus pass
+def collect(config, result_path, source, syn_dir=None, ref_dir=None, trim=True):
+    """The pairs of `source`'s lines (`basename|speaker|...`): -> (items [dict(basename, speaker, ref, syn, window)], skipped
+    [(basename, reason)]).  The reference is `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`), the synthesized
+    file `{result_path}/{basename}.wav` (or in `syn_dir`).  With `trim` and a TextGrid the reference is cut to the speech window
+    `Preprocessor.get_alignment` gives (the window the training mel came from): window = "textgrid"; else "whole"."""
+    from .preprocess import Preprocessor, read_textgrid
+    sr = config["preprocessing"]["audio"]["sampling_rate"]
+    hop = config["preprocessing"]["stft"]["hop_length"]
+    half = config["preprocessing"]["stft"]["filter_length"] // 2
+    items, skipped = [], []
+    with open(source, encoding="utf-8") as f:
+        lines = [ln.strip("\n") for ln in f if ln.strip()]
+    for ln in lines:
+        parts = ln.split("|")
+        if len(parts) < 2:
+            skipped.append((parts[0], "no speaker field"))
+            continue
+        basename, speaker = parts[0], parts[1]
+        ref = os.path.join(ref_dir, basename + ".wav") if ref_dir else os.path.join(config["path"]["raw_path"], speaker, basename + ".wav")
+        syn = os.path.join(syn_dir or result_path, basename + ".wav")
+        missing = [p for p in (ref, syn) if not os.path.exists(p)]
+        if missing:
+            skipped.append((basename, "missing " + ", ".join(missing)))
+            continue
+        r, s = load_audio(ref, sr), load_audio(syn, sr)
+        window = "whole"
+        tg = os.path.join(config["path"]["preprocessed_path"], "TextGrid", speaker, basename + ".TextGrid")
+        if trim and os.path.exists(tg):
+            tiers = read_textgrid(tg)
+            if "phones" in tiers:
+                _, _, start, end = Preprocessor.get_alignment(_Rates(sr, hop), tiers["phones"])
+                if start < end:
+                    r, window = r[int(sr * start):int(sr * end)], "textgrid"
+        reason = None
+        for name, w in (("reference", r), ("synthesized", s)):
+            if len(w) <= half:
+                reason = f"{name} has {len(w)} samples, the STFT needs more than {half}"
+            elif len(w) // hop + 1 > MAX_FRAMES:
+                reason = f"{name} has {len(w) // hop + 1} frames, more than the supported {MAX_FRAMES}"
+        if reason:
+            skipped.append((basename, reason))
+            continue
+        items.append({"basename": basename, "speaker": speaker, "ref": r, "syn": s, "window": window})
+    return items, skipped
+
+
+class _Rates:
+    """What `Preprocessor.get_alignment` reads of its instance."""
+
+    def __init__(self, sampling_rate, hop_length):
+        self.sampling_rate, self.hop_length = sampling_rate, hop_length
+
+
+def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=13, score_fn=None,
+        device="cuda"):
+    """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
+    replaces the device stage.  Returns (rows, skipped, summary)."""
+    import json
+    pp = config["preprocessing"]
+    sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
+    items, skipped = collect(config, result_path, source, syn_dir, ref_dir, trim)
+    if score_fn is None:
+        from . import audio as Audio
+        stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], pp["mel"]["n_mel_channels"], sr,
+                                  pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
+        score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device)       # noqa: E731
+    scores = score_fn([it["ref"] for it in items], [it["syn"] for it in items]) if items else []
+    rows = [{"basename": it["basename"], "speaker": it["speaker"], "reference_window": it["window"], **sc}
+            for it, sc in zip(items, scores)]
+    if out_path:
+        with open(out_path, "w", encoding="utf-8") as f:
+            for row in rows:
+                f.write(json.dumps(row) + "\n")
+    summary = summarize(rows)
+    summary["skipped"] = len(skipped)
+    summary["reference_window"] = {k: sum(1 for r in rows if r["reference_window"] == k) for k in ("textgrid", "whole")}
+    return rows, skipped, summary

@@ -415,6 +415,34 @@ int fs2_align_backtrack(const uint8_t* bp, long ldp_b, long ldp_t, const int32_t
                         const int32_t* block, long ldg, const int32_t* end, int32_t* frames, int nbmax, int B, int Tmax, int Jmax,
                         fs2_stream_t stream);
 
+/* ---- objective scoring: cepstra, dynamic time warping, F0 along the path (specification: fastspeech2_amd/metrics.py) ----
+ * fp64 throughout, ragged batches of pairs: pair p has alens[p] reference frames (index i) and blens[p] synthesized frames (index j),
+ * int32 on the device, both at most fs2_dtw_max_frames() (T1max / T2max above it are FS2_EINVAL).  Cepstra are [B][Tmax][K] with
+ * batch / frame strides in elements.  Local costs (f64) and backpointers (bytes) of a pair are stored skewed: cell (i, j) is at row
+ * (i + j) mod blens[p], column i of a [T2max][>= T1max] matrix (row stride ld*_s >= T1max, pair stride ld*_b >= T2max ld*_s), so an
+ * anti-diagonal is contiguous in i.  Nothing at i >= alens[p] or a row >= blens[p] is read or written.  No atomics. */
+int fs2_dtw_max_frames(void);
+/* log-mel [B][n_mel][frames] f32 (strides ldm_b, ldm_c) -> c[b][t][k] = sum_m mel[b][m][t] table[k][m] in ascending m, k < K <= 40;
+ * table [K][n_mel] f64 (n_mel <= 128) is the caller's DCT rows: no cosine is evaluated on the device */
+int fs2_mcep(const float* mel, long ldm_b, long ldm_c, const int32_t* lens, const double* table, int K, double* c, long ldc_b,
+             long ldc_t, int B, int n_mel, int Tmax, fs2_stream_t stream);
+/* d(i, j) = sqrt(sum_k (a[p][i][k] - b[p][j][k])^2), k ascending, unfused, correctly rounded root; skewed */
+int fs2_dtw_cost(const double* a, long lda_b, long lda_t, const int32_t* alens, const double* b, long ldb_b, long ldb_t,
+                 const int32_t* blens, int K, double* cost, long ldd_b, long ldd_s, int B, int T1max, int T2max, fs2_stream_t stream);
+/* D(0,0) = d(0,0), D(i,j) = d(i,j) + min(D(i-1,j-1), D(i-1,j), D(i,j-1)); bp = 0 / 1 / 2 in that order, lowest code on ties, skewed
+ * like cost; total[p] = D(alens[p] - 1, blens[p] - 1).  D itself is never stored. */
+int fs2_dtw_scan(const double* cost, long ldd_b, long ldd_s, const int32_t* alens, const int32_t* blens, uint8_t* bp, long ldp_b,
+                 long ldp_s, double* total, int B, int T1max, int T2max, fs2_stream_t stream);
+/* the path from (0, 0) to (alens[p] - 1, blens[p] - 1): pi / pj [B][ldq] int32 (ldq >= T1max + T2max - 1), plen[p] = P cells;
+ * entries [P, alens[p] + blens[p] - 1) are set to -1, later ones are left alone */
+int fs2_dtw_backtrack(const uint8_t* bp, long ldp_b, long ldp_s, const int32_t* alens, const int32_t* blens, int32_t* pi, int32_t* pj,
+                      long ldq, int32_t* plen, int B, int T1max, int T2max, fs2_stream_t stream);
+/* sums[p][0..3) = {cells where exactly one of r = f0_ref[p][pi], s = f0_syn[p][pj] is 0, cells with r > 0 and s > 0, the sum over
+ * those of (1200 log2(s / r))^2}, in a fixed order of additions */
+int fs2_dtw_f0(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* plen, const double* f0_ref, long ldr,
+               const double* f0_syn, long lds, const int32_t* alens, const int32_t* blens, double* sums, long ldo, int B, int T1max,
+               int T2max, fs2_stream_t stream);
+
 /* ---- loss (model/loss.py:19-92): masked L1 (mel, post-net mel) + masked MSE (pitch, energy, log-duration) ----
  * mel / post: [B][T][n_mel] f32 predictions; mel_t: target with batch stride ld_t_b (its own padded length >= T);
  * lens int64 (valid = t < min(len, T)); p/e predictions [B][L] (phoneme level) or [B][T] (p_frame / e_frame = 1) with

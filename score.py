@@ -1,0 +1,54 @@
+#!/usr/bin/env python
+"""score.py — objective scores of synthesized against recorded speech on the GPU (fastspeech2_amd/metrics.py):
+
+    python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
+                    [--n_mcep 13] [--out scores.jsonl]
+
+For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
+is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
+distortion along a dynamic-time-warping path, F0 RMSE in cents and voiced / unvoiced error on that path.  The recorded file is cut
+to its TextGrid's speech window, the window the training mel came from, unless `--no_trim` is given or there is no TextGrid; every
+output row says which was used.  One JSON object per utterance goes to `--out`, one summary line to stdout.  The cepstra are a DCT
+of this project's own log-mel: the dB values compare runs of this tool, not published MCD figures."""
+import argparse
+import json
+import sys
+
+import yaml
+
+from fastspeech2_amd import metrics
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("-p", "--preprocess_config", type=str, required=True, help="path to preprocess.yaml")
+    parser.add_argument("-t", "--train_config", type=str, required=True, help="path to train.yaml (path.result_path)")
+    parser.add_argument("--source", type=str, required=True, help="metadata file of `basename|speaker|...` lines (val.txt)")
+    parser.add_argument("--syn_dir", type=str, default=None, help="folder of the synthesized wavs (default: train.yaml's result_path)")
+    parser.add_argument("--ref_dir", type=str, default=None, help="folder of the recorded wavs (default: raw_path/speaker)")
+    parser.add_argument("--no_trim", action="store_true", help="use the whole recorded file, not its TextGrid's speech window")
+    parser.add_argument("--no_f0", action="store_true", help="mel-cepstral distortion only")
+    parser.add_argument("--n_mcep", type=int, default=13, help="cepstral coefficients 1..n_mcep (at most 40)")
+    parser.add_argument("--out", type=str, default="scores.jsonl")
+    parser.add_argument("--device", type=str, default="cuda")
+    return parser.parse_args(argv)
+
+
+def main(argv=None, score_fn=None):
+    args = parse_args(argv)
+    config = yaml.load(open(args.preprocess_config, "r"), Loader=yaml.FullLoader)
+    train = yaml.load(open(args.train_config, "r"), Loader=yaml.FullLoader)
+    try:
+        rows, skipped, summary = metrics.run(config, train["path"]["result_path"], args.source, out_path=args.out, syn_dir=args.syn_dir,
+                                             ref_dir=args.ref_dir, trim=not args.no_trim, f0=not args.no_f0, n_mcep=args.n_mcep,
+                                             score_fn=score_fn, device=args.device)
+    except ValueError as e:
+        sys.exit(str(e))
+    for name, reason in skipped:
+        print("skipped {}: {}".format(name, reason))
+    print(json.dumps(summary))
+    return rows, skipped, summary
+
+
+if __name__ == "__main__":
+    main()
