@@ -19,6 +19,7 @@ import torch
 
 from oracle.weights import seeded_state_dict, synthetic_batch
 from tests.golden import configs
+from tests.gemm_ref import assert_rounding_only, conv_reference
 from tests.helpers import make_model
 
 pytestmark = pytest.mark.gpu
@@ -39,36 +40,9 @@ def ragged_lens(S, seed=5):
 
 
 def conv_ref_gpu(x, w_tap_major, bias, S, pad, lens=None):
-    """exact-product reference on the device: y[m] = sum_j x[m + j - pad] @ W[:, j, :].T (+bias), taps outside the row's own
-    sequence contribute 0; fp32 operands (bf16 values are exact in fp32), fp32 matmuls, summed over taps in fp64."""
-    Bq = x.shape[0] // S
-    k = w_tap_major.shape[1]
-    xs = x.float().view(Bq, S, -1)
-    y = torch.zeros(Bq, S, w_tap_major.shape[0], device=x.device, dtype=torch.float64)
-    for j in range(k):
-        sh = j - pad
-        lo, hi = max(0, -sh), min(S, S - sh)
-        if hi <= lo:
-            continue
-        y[:, lo:hi] += (xs[:, lo + sh:hi + sh] @ w_tap_major[:, j, :].float().t()).double()
-    if bias is not None:
-        y += bias.double()
-    y = y.view(Bq * S, -1)
-    if lens is not None:
-        pad_rows = (torch.arange(S, device=x.device).unsqueeze(0) >= lens.to(x.device).unsqueeze(1)).reshape(-1)
-        y[pad_rows] = 0
-    return y
-
-
-def assert_rounding_only(y, ref, dtype, what):
-    """|y - ref| <= 1 ulp of the storage type relative to |ref| (+ an absolute floor for cancelling sums)."""
-    ref = ref.double()
-    scale = ref.abs().max().item()
-    ulp = BF16_ULP if dtype == torch.bfloat16 else 2.0 ** -20
-    err = (y.double() - ref).abs()
-    bound = ulp * ref.abs() + (2e-4 if dtype == torch.bfloat16 else 2e-5) * scale
-    bad = (err > bound)
-    assert not bad.any(), (what, int(bad.sum()), err.max().item(), scale)
+    """exact-product reference on the device (tests/gemm_ref.py): y[m] = sum_j x[m + j - pad] @ W[:, j, :].T (+bias), taps outside the
+    row's own sequence contribute 0; fp32 operands (bf16 values are exact in fp32), fp32 matmuls, summed over taps in fp64."""
+    return conv_reference(x, w_tap_major, bias, S, pad=pad, lens=lens)
 
 
 # (name, Cin, Cout, k, S): every contraction of the 4+4 train step that runs at M = B*S rows
@@ -204,19 +178,10 @@ def test_vocoder_convs_with_leaky_relu_prologue(dev, name, C, N, k, dil, S, Bq):
 # Config 5 (batch synthesis, bf16 vocoder): the kernels the RTF is quoted on, pinned at synthesis size
 # ---------------------------------------------------------------------------------------------------------------------------
 def dilated_conv_ref(xa, w, bias, Bq, S, k, dil, pad):
-    """exact-product reference of a dilated Conv1d on rows: xa (M, C) f32 holding bf16 values (activation already applied and
-    rounded as the kernel's prologue does), w (N, k, C) bf16.  fp32 matmuls per tap, summed over taps in fp64."""
-    M, C = xa.shape
-    xs = xa.view(Bq, S, C)
-    ref = torch.zeros(Bq, S, w.shape[0], device=xa.device, dtype=torch.float64)
-    for j in range(k):
-        sh = j * dil - pad
-        lo, hi = max(0, -sh), min(S, S - sh)
-        if hi > lo:
-            ref[:, lo:hi] += (xs[:, lo + sh:hi + sh] @ w[:, j, :].float().t()).double()
-    if bias is not None:
-        ref += bias.double()
-    return ref.view(M, -1)
+    """exact-product reference of a dilated Conv1d on rows (tests/gemm_ref.py): xa (M, C) f32 holding bf16 values (activation already
+    applied and rounded as the kernel's prologue does), w (N, k, C) bf16.  fp32 matmuls per tap, summed over taps in fp64."""
+    assert xa.shape[0] == Bq * S and w.shape[1] == k
+    return conv_reference(xa, w, bias, S, dil=dil, pad=pad)
 
 
 def _variant(ops, x, y, res, M, N, C, S, k, dil, in_act, in_slope):

@@ -76,6 +76,44 @@ def test_dispatch_queries_are_pure_host_functions():
     assert lib.fs2_conv_gemm_variant(256, 768, 0, 0, 0, 48 * 925, 768, 256, 925, 1, 1, 0, 0.0, BF16) == 9
 
 
+# The dispatch of every contraction the bench runs, recorded before tests/test_gemm_dispatch_gpu.py was added: a predicate narrowed
+# for a small or odd shape must leave these where they are.  (name, Cin, Cout, k, S, codes) at M = 48 S; codes: bf16 then fp32, each
+# forward (Cin -> Cout) then data gradient (Cout -> Cin), each without lens / with lens / with lens and tile map.  256 compute
+# units: the library's answer without a device, and the MI355X's.
+BENCH_DISPATCH = [
+    ("ffn w_1 k9", 256, 1024, 9, 925, (5, 3, 5, 5, 3, 5, 2, 2, 2, 2, 2, 2)),
+    ("ffn w_2 k1", 1024, 256, 1, 925, (7, 7, 7, 9, 9, 9, 1, 1, 1, 1, 1, 1)),
+    ("qkv", 256, 768, 1, 925, (9, 9, 9, 7, 7, 7, 1, 1, 1, 1, 1, 1)),
+    ("fc", 256, 256, 1, 925, (9, 9, 9, 9, 9, 9, 1, 1, 1, 1, 1, 1)),
+    ("postnet k5", 512, 512, 5, 925, (5, 3, 5, 5, 3, 5, 2, 2, 2, 2, 2, 2)),
+    ("postnet in", 80, 512, 5, 925, (2, 2, 2, 5, 3, 5, 2, 2, 2, 2, 2, 2)),
+    ("postnet out", 512, 80, 5, 925, (5, 3, 5, 2, 2, 2, 2, 2, 2, 2, 2, 2)),
+    ("mel", 256, 80, 1, 925, (6, 1, 6, 1, 1, 1, 1, 1, 1, 1, 1, 1)),
+    ("enc w_1 k9", 256, 1024, 9, 128, (5, 3, 5, 5, 2, 5, 2, 2, 2, 2, 2, 2)),
+    ("predictor k3", 256, 256, 3, 128, (2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2)),
+]
+# the bf16 vocoder at batch-synthesis size (C, N, k, dil, S, B): (leaky-ReLU prologue, residual operand) -> code
+VOCODER_DISPATCH = [
+    (256, 256, 7, 3, 7200, 8, (5, 5)), (128, 128, 11, 5, 57600, 4, (5, 5)), (128, 128, 3, 1, 57600, 4, (5, 5)), (256, 256, 11, 1, 7200, 8, (5, 5)),
+    (512, 2048, 3, 1, 900, 8, (5, 5)), (256, 1024, 3, 1, 7200, 8, (5, 5)), (128, 128, 3, 1, 57600, 8, (5, 5)),
+    (64, 64, 3, 1, 115200, 8, (4, 4)), (64, 64, 7, 3, 115200, 8, (4, 4)), (64, 64, 11, 5, 115200, 8, (4, 4)),
+    (32, 32, 3, 1, 230400, 8, (4, 4)), (32, 32, 7, 3, 230400, 8, (4, 4)), (32, 32, 11, 5, 230400, 8, (4, 4)),
+]
+
+
+def test_dispatch_of_the_bench_and_vocoder_shapes_is_pinned():
+    lib = _lib.load()
+    for name, Cin, Cout, k, S, codes in BENCH_DISPATCH:
+        M = 48 * S
+        got = tuple(lib.fs2_conv_gemm_variant(ci, co, 0, hl, hm, M, co, ci, S, k, 1, 0, 0.0, dt)
+                    for dt in (1, 0) for ci, co in ((Cin, Cout), (Cout, Cin)) for hl, hm in ((0, 0), (1, 0), (1, 1)))
+        assert got == codes, (name, got, codes)
+    for C, N, k, dil, S, B, codes in VOCODER_DISPATCH:
+        M = B * S
+        got = (lib.fs2_conv_gemm_variant(C, N, 0, 0, 0, M, N, C, S, k, dil, 3, 0.1, 1), lib.fs2_conv_gemm_variant(C, N, N, 0, 0, M, N, C, S, k, dil, 0, 0.0, 1))
+        assert got == codes, ((C, N, k, dil, S, B), got, codes)
+
+
 def test_no_copy_of_an_in_flight_fragment_register_in_the_persistent_kernel():
     """The persistent contraction kernel tracks its LDS fragment reads by hand (inline-asm ds_read_b128 + counted lgkmcnt); the
     compiler does not know that such a register may still be in flight, so a register-to-register copy of one between its read and
