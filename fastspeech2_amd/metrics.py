@@ -4,7 +4,11 @@
 
 WHAT THE NUMBERS ARE.  The cepstra are a DCT of this project's own 80-band natural-log mel spectrogram (`audio.TacotronSTFT`), not
 WORLD / SPTK mel-cepstra of a spectral envelope.  The dB values compare two runs of this tool with each other; they are not
-comparable with MCD figures published elsewhere.
+comparable with MCD figures published elsewhere.  That is `cepstra="mel"`, the default.  With `cepstra="world"` (`score.py --cepstra
+world`) the cepstra are instead the mel-cepstra c~_1 .. c~_K of the CheapTrick spectral envelope at the utterance's own F0
+(`envelope`, specified in full in its docstring): the published definition, independent of pitch, held against an fp64 numpy
+restatement and analytic answers; its agreement with the pyworld / pysptk binaries is unmeasured.  Everything from the DTW on is the
+same for both.
 
 Cepstra.  x[m][t] is the log-mel (B, n_mel, T) exactly as `TacotronSTFT.mel_spectrogram_ragged` returns it, with its frame counts.
 c[k][t] = sum_m x[m][t] C[k][m], m ascending, with the orthonormal DCT-II rows C[k][m] = sqrt(2 / n_mel) cos(pi k (2 m + 1) / (2 n_mel)),
@@ -254,10 +258,11 @@ def summarize(rows):
     return out
 
 
-def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256):
+def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0):
     """What a batch of n pairs padded to (T1, T2) frames holds on the device: 9 B per (i, j) cell (local cost + backpointer), the
-    audio, its STFT workspace and mel (about 40 B per sample), cepstra, F0 and the path."""
-    return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64))
+    audio, its STFT workspace and mel (about 40 B per sample), cepstra, F0 and the path; with `fft_size` (cepstra="world") also the
+    spectral envelope, fft_size / 2 + 1 float64 bins per frame and side."""
+    return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64 + (fft_size // 2 + 1) * 8 * (fft_size > 0)))
 
 
 def load_audio(path, sampling_rate):
@@ -277,39 +282,61 @@ def frame_counts(n_samples, sampling_rate, hop_length, f0=True):
     return min(T, frame_count(n_samples, sampling_rate, hop_length / sampling_rate * 1000)) if f0 else T
 
 
-def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=13, f0=True, device="cuda", budget=4 << 30):
+def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None, f0=True, device="cuda", budget=4 << 30,
+                cepstra="mel", alpha=None):
     """Scores of (recorded, synthesized) pairs of float32 waveforms at `sampling_rate` -> one dict per pair (module docstring), in
     the order given.  `stft` is the config's `audio.TacotronSTFT`.  Pairs are packed longest first into ragged batches under `budget`
     bytes of device buffers; per batch: both sides through one pinned staging buffer, mel -> cepstra -> local cost -> scan ->
-    backtrack (and DIO + StoneMask -> the path sums with `f0`), one D2H copy of the scores."""
+    backtrack (and DIO + StoneMask -> the path sums with `f0`), one D2H copy of the scores.  With cepstra="world" the cepstra are
+    `envelope.world_cepstra` (n_mcep 24 by default, all-pass constant `alpha` or the table's) of the unclamped audio at its DIO +
+    StoneMask F0, which is then always extracted, on DIO's frame grid, and only reported with `f0`; no mel is taken and `stft` may
+    be None.  Every row then also carries cepstra, alpha and fft_size."""
+    from . import envelope as Env
+    if cepstra not in ("mel", "world"):
+        raise ValueError(f"cepstra must be 'mel' or 'world', got {cepstra!r}")
+    world = cepstra == "world"
     if len(ref_wavs) != len(syn_wavs):
         raise ValueError(f"{len(ref_wavs)} reference and {len(syn_wavs)} synthesized waveforms")
-    if hop_length != stft.hop_length:
+    if stft is not None and hop_length != stft.hop_length:
         raise ValueError(f"hop_length {hop_length} is not the STFT's {stft.hop_length}")
-    dct_table(stft.n_mel_channels, n_mcep)                                  # validates n_mcep before any work
-    fr = [frame_counts(len(w), sampling_rate, hop_length, f0) for w in ref_wavs]
-    fs = [frame_counts(len(w), sampling_rate, hop_length, f0) for w in syn_wavs]
+    fft_size = 0
+    if world:
+        n_mcep = Env.check_mcep(Env.DEFAULT_MCEP if n_mcep is None else n_mcep)
+        fft_size, alpha = Env.fft_size(sampling_rate), Env.alpha_for(sampling_rate, alpha)
+        empty = [len(w) for w in list(ref_wavs) + list(syn_wavs) if len(w) < 1]
+        if empty:
+            raise ValueError("a waveform without samples has no spectral envelope")
+    else:
+        if stft is None or alpha is not None:
+            raise ValueError("cepstra='mel' needs the STFT and takes no alpha")
+        n_mcep = 13 if n_mcep is None else n_mcep
+        dct_table(stft.n_mel_channels, n_mcep)                              # validates n_mcep before any work
+    fr = [frame_counts(len(w), sampling_rate, hop_length, f0 or world) for w in ref_wavs]
+    fs = [frame_counts(len(w), sampling_rate, hop_length, f0 or world) for w in syn_wavs]
     check_frames(fr, fs)
-    short = [len(w) for w in list(ref_wavs) + list(syn_wavs) if len(w) <= stft.filter_length // 2]
+    short = [] if world else [len(w) for w in list(ref_wavs) + list(syn_wavs) if len(w) <= stft.filter_length // 2]
     if short:
         raise ValueError(f"a waveform of {short[0]} samples is too short for the STFT's reflect padding ({stft.filter_length // 2})")
     dev = ragged.require_device(torch.device(device), WHO)
     staging = ragged.Staging()
     frame_period = hop_length / sampling_rate * 1000
     rows = [None] * len(ref_wavs)
+    cepstra_fn = globals()["cepstra"]                                       # the argument `cepstra` shadows the module's function
 
     def side(wavs, frames):
         staging.pack(wavs)
         y, lens = staging.to(dev), [len(w) for w in wavs]
+        track = None
+        if f0 or world:
+            from . import pitch as Pitch
+            f, _, f_frames = Pitch.dio(y, lens, sampling_rate, frame_period)
+            track = Pitch.stonemask(y, lens, f, f_frames, sampling_rate, frame_period)
+        if world:
+            return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), track if f0 else None
         mel, _, _ = stft.mel_spectrogram_ragged(y.clamp(-1.0, 1.0), lens)
-        c = cepstra(mel, frames, n_mcep)
-        if not f0:
-            return c, None
-        from . import pitch as Pitch
-        f, _, f_frames = Pitch.dio(y, lens, sampling_rate, frame_period)
-        return c, Pitch.stonemask(y, lens, f, f_frames, sampling_rate, frame_period)
+        return cepstra_fn(mel, frames, n_mcep), track
 
-    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length)     # noqa: E731
+    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size)     # noqa: E731
     for batch in ragged.greedy_batches(list(zip(fr, fs)), budget, cost):
         al, bl = [fr[i] for i in batch], [fs[i] for i in batch]
         a, f0a = side([ref_wavs[i] for i in batch], al)
@@ -321,6 +348,8 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=13, 
         host = torch.stack(cols, dim=1).cpu().numpy()                       # the batch's one D2H copy
         for r, i in enumerate(batch):
             rows[i] = scores_from_sums(host[r, 0], host[r, 1], al[r], bl[r], host[r, 2:5] if f0 else None)
+            if world:
+                rows[i].update(cepstra="world", alpha=alpha, fft_size=fft_size)
     return rows
 
 
@@ -378,19 +407,28 @@ class _Rates:
         self.sampling_rate, self.hop_length = sampling_rate, hop_length
 
 
-def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=13, score_fn=None,
-        device="cuda"):
+def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=None, score_fn=None,
+        device="cuda", cepstra="mel", alpha=None):
     """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
-    replaces the device stage.  Returns (rows, skipped, summary)."""
+    replaces the device stage.  Returns (rows, skipped, summary).  With cepstra="world" the rows and the summary also say cepstra,
+    alpha and fft_size; with "mel" they are what they were before that choice existed."""
     import json
     pp = config["preprocessing"]
     sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
+    world_keys = {}
+    if cepstra == "world":                                                  # refused before a file is read
+        from . import envelope as Env
+        Env.check_mcep(Env.DEFAULT_MCEP if n_mcep is None else n_mcep)
+        world_keys = {"cepstra": "world", "alpha": Env.alpha_for(sr, alpha), "fft_size": Env.fft_size(sr)}
+    elif cepstra != "mel" or alpha is not None:
+        raise ValueError(f"cepstra must be 'mel' (without alpha) or 'world', got {cepstra!r}, alpha={alpha}")
     items, skipped = collect(config, result_path, source, syn_dir, ref_dir, trim)
     if score_fn is None:
         from . import audio as Audio
         stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], pp["mel"]["n_mel_channels"], sr,
                                   pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
-        score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device)       # noqa: E731
+        score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device, cepstra=cepstra,     # noqa: E731
+                                            alpha=alpha)
     scores = score_fn([it["ref"] for it in items], [it["syn"] for it in items]) if items else []
     rows = [{"basename": it["basename"], "speaker": it["speaker"], "reference_window": it["window"], **sc}
             for it, sc in zip(items, scores)]
@@ -399,6 +437,7 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
             for row in rows:
                 f.write(json.dumps(row) + "\n")
     summary = summarize(rows)
+    summary.update(world_keys)
     summary["skipped"] = len(skipped)
     summary["reference_window"] = {k: sum(1 for r in rows if r["reference_window"] == k) for k in ("textgrid", "whole")}
     return rows, skipped, summary

@@ -443,6 +443,23 @@ int fs2_dtw_f0(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* pl
                const double* f0_syn, long lds, const int32_t* alens, const int32_t* blens, double* sums, long ldo, int B, int T1max,
                int T2max, fs2_stream_t stream);
 
+/* ---- spectral envelope (CheapTrick) and its mel-cepstrum (specification: fastspeech2_amd/envelope.py) ----
+ * fp64 throughout, ragged: row b has lens[b] samples of the float32 batch x (row stride ldx) and frames[b] frames (int32, device);
+ * f0 [B][ldf] f64, one value per frame; spectra [B][Fmax][N / 2 + 1] with batch / frame strides in elements, N a power of two in
+ * [256, 2048]; twiddle [N / 2][2] = {cos, -sin}(2 pi k / N) is the caller's table: no sine is evaluated for a transform.  Nothing
+ * at a frame >= frames[b] or a sample >= lens[b] is read or written.  No atomics, fixed-order sums.
+ * fs2_env_spectrum: P[b][f] = DC-corrected power spectrum of the clamped, Hann-windowed, mean-removed frame at f frame_period ms. */
+int fs2_env_spectrum(const float* x, long ldx, const int32_t* lens, const double* f0, long ldf, const int32_t* frames, double fs,
+                     double frame_period, const double* twiddle, int N, double* P, long ldp_b, long ldp_t, int B, int Fmax, int Nmax,
+                     fs2_stream_t stream);
+/* in place, P -> envelope: linear smoothing of width 2 f0 / 3, + env_floor, then the sinc and recovery (q1) lifters on its cepstrum */
+int fs2_env_smooth(const double* f0, long ldf, const int32_t* frames, double fs, const double* twiddle, int N, double q1,
+                   double env_floor, double* P, long ldp_b, long ldp_t, int B, int Fmax, fs2_stream_t stream);
+/* c[b][f][m - 1] = sum_q table[m - 1][q] c_q, m = 1 .. K <= 40, c_q the one-sided cepstrum of 0.5 ln env[b][f]; table [K][N / 2 + 1]
+ * is the caller's freqt recursion applied to the unit vectors; c [B][Fmax][K] in the row layout fs2_dtw_cost reads */
+int fs2_env_mcep(const double* env, long lde_b, long lde_t, const int32_t* frames, const double* twiddle, int N, const double* table,
+                 int K, double* c, long ldc_b, long ldc_t, int B, int Fmax, fs2_stream_t stream);
+
 /* ---- loss (model/loss.py:19-92): masked L1 (mel, post-net mel) + masked MSE (pitch, energy, log-duration) ----
  * mel / post: [B][T][n_mel] f32 predictions; mel_t: target with batch stride ld_t_b (its own padded length >= T);
  * lens int64 (valid = t < min(len, T)); p/e predictions [B][L] (phoneme level) or [B][T] (p_frame / e_frame = 1) with

@@ -2,14 +2,17 @@
 """score.py — objective scores of synthesized against recorded speech on the GPU (fastspeech2_amd/metrics.py):
 
     python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
-                    [--n_mcep 13] [--out scores.jsonl]
+                    [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--out scores.jsonl]
 
 For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
 is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
 distortion along a dynamic-time-warping path, F0 RMSE in cents and voiced / unvoiced error on that path.  The recorded file is cut
 to its TextGrid's speech window, the window the training mel came from, unless `--no_trim` is given or there is no TextGrid; every
-output row says which was used.  One JSON object per utterance goes to `--out`, one summary line to stdout.  The cepstra are a DCT
-of this project's own log-mel: the dB values compare runs of this tool, not published MCD figures."""
+output row says which was used.  One JSON object per utterance goes to `--out`, one summary line to stdout.  With `--cepstra mel`
+(the default, 13 coefficients) the cepstra are a DCT of this project's own log-mel: the dB values compare runs of this tool, not
+published MCD figures.  With `--cepstra world` (24 coefficients) they are mel-cepstra of the CheapTrick spectral envelope, the
+published definition (fastspeech2_amd/envelope.py); the all-pass constant comes from the sampling rate unless `--alpha` gives it, and
+rows and summary also carry `cepstra`, `alpha` and `fft_size`.  Agreement with the pyworld / pysptk binaries is unmeasured."""
 import argparse
 import json
 import sys
@@ -28,7 +31,10 @@ def parse_args(argv=None):
     parser.add_argument("--ref_dir", type=str, default=None, help="folder of the recorded wavs (default: raw_path/speaker)")
     parser.add_argument("--no_trim", action="store_true", help="use the whole recorded file, not its TextGrid's speech window")
     parser.add_argument("--no_f0", action="store_true", help="mel-cepstral distortion only")
-    parser.add_argument("--n_mcep", type=int, default=13, help="cepstral coefficients 1..n_mcep (at most 40)")
+    parser.add_argument("--cepstra", choices=("mel", "world"), default="mel",
+                        help="mel: DCT of the log-mel (tool-internal); world: mel-cepstra of the CheapTrick spectral envelope")
+    parser.add_argument("--alpha", type=float, default=None, help="all-pass constant of --cepstra world (default: by sampling rate)")
+    parser.add_argument("--n_mcep", type=int, default=None, help="cepstral coefficients 1..n_mcep (at most 40; default 13 mel, 24 world)")
     parser.add_argument("--out", type=str, default="scores.jsonl")
     parser.add_argument("--device", type=str, default="cuda")
     return parser.parse_args(argv)
@@ -41,7 +47,7 @@ def main(argv=None, score_fn=None):
     try:
         rows, skipped, summary = metrics.run(config, train["path"]["result_path"], args.source, out_path=args.out, syn_dir=args.syn_dir,
                                              ref_dir=args.ref_dir, trim=not args.no_trim, f0=not args.no_f0, n_mcep=args.n_mcep,
-                                             score_fn=score_fn, device=args.device)
+                                             score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha)
     except ValueError as e:
         sys.exit(str(e))
     for name, reason in skipped:
