@@ -165,6 +165,29 @@ def resstage_fwd(x, blocks, B, S, dilations, out_scale=1.0 / 3, slope=0.1, post_
     return xs
 
 
+def melgan_guard_rows(src, dst, G, reflect=True, interior=True):
+    """guard rows of a [B][G + S + G][C] activation buffer (fs2_melgan_guard_rows).  src: (B, S, C) view of the rows [0, S) (any row /
+    item stride), dst: (B, S + 2G, C) view.  Rows outside [0, S) <- reflection (F.pad(mode="reflect")) or zeros; interior=False
+    writes the guard rows only (src is dst's own interior)."""
+    B, S, C = src.shape
+    assert dst.shape == (B, S + 2 * G, C) and src.stride(2) == 1 and dst.stride(2) == 1 and src.dtype == dst.dtype
+    _lib.call("fs2_melgan_guard_rows", _p(src), src.stride(1), src.stride(0), _p(dst), dst.stride(1), dst.stride(0), B, S, G, C,
+              int(reflect), int(interior), dt(src), _stream())
+    return dst
+
+
+def melgan_stage_fwd(x, w, bias, y, dilations=(1, 3, 9), slope=0.2, out_slope=0.0):
+    """the three ResnetBlocks of a narrow MelGAN stage in one launch (fs2_melgan_stage_fwd; C in {32, 64}, bf16).  x, y: (B, S, C)
+    views (any row / item stride); w: [3][5C][C], bias: [3][2][C] f32 (melgan.Generator packs them)."""
+    B, S, C = x.shape
+    assert y.shape == x.shape and x.stride(2) == 1 and y.stride(2) == 1 and w.shape == (3, 5 * C, C) and w.is_contiguous()
+    assert bias.shape == (3, 2, C) and bias.is_contiguous() and bias.dtype == torch.float32 and w.dtype == x.dtype == y.dtype
+    d0, d1, d2 = dilations
+    _lib.call("fs2_melgan_stage_fwd", _p(x), x.stride(1), x.stride(0), _p(w), _p(bias), _p(y), y.stride(1), y.stride(0), slope, out_slope,
+              B, S, C, d0, d1, d2, dt(x), _stream())
+    return y
+
+
 def tail_workspace(device):
     """scratch for conv_gemm(..., tail_ws=): fs2_conv_gemm_tail_ws_bytes() bytes of f32 (one 256x128 slab per CU).  One per stream
     of contraction launches (launches sharing it must not run concurrently)."""

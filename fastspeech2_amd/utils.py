@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from . import hifigan
+from . import hifigan, melgan
 from .model import FastSpeech2, ScheduledOptim
 
 # hifigan/config.json of the reference (HiFi-GAN V1) — used when no config file sits next to the checkpoint
@@ -67,12 +67,28 @@ def get_param_num(model):
     return sum(param.numel() for param in model.parameters())
 
 
-def get_vocoder(config, device, hifigan_dir="hifigan", compute_dtype="fp32", allow_random_init=False):
-    """utils/model.py:42-71 (HiFi-GAN branch; MelGAN is a torch.hub download and out of scope)."""
+MELGAN_FILES = {"LJSpeech": "linda_johnson.pt", "universal": "multi_speaker.pt"}
+
+
+def get_vocoder(config, device, hifigan_dir="hifigan", compute_dtype="fp32", allow_random_init=False, melgan_dir="melgan"):
+    """utils/model.py:42-71.  HiFi-GAN: `{hifigan_dir}/generator_*.pth.tar`.  MelGAN: the reference downloads the generator through
+    torch.hub; here the two weight files that download leaves behind (`linda_johnson.pt` / `multi_speaker.pt`, in the hub cache
+    under `descriptinc_melgan-neurips_master/models/`) are read from `melgan_dir` - nothing is fetched."""
     name = config["vocoder"]["model"]
     speaker = config["vocoder"]["speaker"]
+    if name == "MelGAN":
+        vocoder = melgan.Generator(compute_dtype=compute_dtype)
+        ckpt_path = os.path.join(melgan_dir, MELGAN_FILES[speaker])
+        if os.path.exists(ckpt_path):
+            vocoder.load_state_dict(torch.load(ckpt_path, map_location="cpu", weights_only=True))
+        elif not allow_random_init:
+            raise FileNotFoundError(ckpt_path)
+        vocoder.eval()
+        vocoder.remove_weight_norm()
+        vocoder.to(device)
+        return vocoder
     if name != "HiFi-GAN":
-        raise NotImplementedError(f"vocoder {name!r}: only HiFi-GAN is built (MelGAN needs torch.hub / network)")
+        raise NotImplementedError(f"vocoder {name!r}: HiFi-GAN and MelGAN are built")
     cfg_path = os.path.join(hifigan_dir, "config.json")
     if os.path.exists(cfg_path):
         with open(cfg_path, "r") as f:
@@ -98,17 +114,22 @@ def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None):
     """utils/model.py:74-92: mels (B, 80, T) -> list of int16 numpy arrays (cut to `lengths` samples).
     (The PCM comes back with a plain `.cpu()`: a cached pinned buffer + asynchronous copy + reading `lengths` behind the vocoder's
     launches was measured twice - r03s: 8.77 vs 8.66 ms per batch, r05q: 7.63 vs 7.59 - and is no faster.)"""
-    name = model_config["vocoder"]["model"]
-    assert name == "HiFi-GAN"
     if torch.is_tensor(lengths):
         lengths = lengths.tolist()
     with torch.no_grad():
-        pcm = vocoder.infer_pcm(mels, preprocess_config["preprocessing"]["audio"]["max_wav_value"])
+        pcm = vocoder.infer_pcm(vocoder_input(mels, model_config), preprocess_config["preprocessing"]["audio"]["max_wav_value"])
     wavs = [w for w in pcm.cpu().numpy()]
     for i in range(len(mels)):
         if lengths is not None:
             wavs[i] = wavs[i][: lengths[i]]
     return wavs
+
+
+def vocoder_input(mels, model_config):
+    """what the vocoder's infer_pcm takes for mels (B, 80, T): HiFi-GAN the mel itself, MelGAN mels / ln 10 (utils/model.py:78)"""
+    name = model_config["vocoder"]["model"]
+    assert name in ("HiFi-GAN", "MelGAN"), name
+    return mels * (1.0 / np.log(10)) if name == "MelGAN" else mels
 
 
 def to_device(data, device):
@@ -208,7 +229,7 @@ class SynthPipeline:
     def __init__(self, model, vocoder, configs, control_values=(1.0, 1.0, 1.0), device=None, path=None, write=False, voc_streams=3):
         self.model, self.vocoder = model, vocoder
         self.preprocess_config, self.model_config = configs[0], configs[1]
-        assert self.model_config["vocoder"]["model"] == "HiFi-GAN"
+        assert self.model_config["vocoder"]["model"] in ("HiFi-GAN", "MelGAN")
         self.controls = control_values
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.index is None:          # "cuda" -> "cuda:N": the vocoder's weight images are cached per RESOLVED device, and a
@@ -243,7 +264,8 @@ class SynthPipeline:
             self._n += 1
             with torch.cuda.stream(s_voc):
                 s_voc.wait_event(ready)
-                pcm = self.vocoder.infer_pcm(out[1].transpose(1, 2), self.preprocess_config["preprocessing"]["audio"]["max_wav_value"])
+                pcm = self.vocoder.infer_pcm(vocoder_input(out[1].transpose(1, 2), self.model_config),
+                                             self.preprocess_config["preprocessing"]["audio"]["max_wav_value"])
                 slot = (self._n - 1) % len(self._pcm_ring)
                 buf = self._pcm_ring[slot]
                 if buf is None or buf.numel() < pcm.numel():

@@ -292,6 +292,24 @@ int fs2_resstage_fwd(const void* x, long ldx, const void* w1a, const void* w2a, 
                      const void* w1b, const void* w2b, const float* b1b, const float* b2b, int kb, const void* w1c,
                      const void* w2c, const float* b1c, const float* b2c, int kc, void* xs, long ldxs, float out_scale,
                      float slope, float post_slope, int B, int S, int C, int d0, int d1, int d2, int dtype, fs2_stream_t stream);
+/* ---- MelGAN generator (fastspeech2_amd/melgan.py states the network) ----
+ * Guard rows for reflection-padded convolutions on the zero-padding contraction kernels: dst holds [B][G + S + G] rows of C channels
+ * (row stride ld_dst, item stride dst_bstride, both in elements); row G + t of item b is src row t (src: row stride ld_src, item
+ * stride src_bstride, pointing at row 0 of item 0).  Guard rows t in [-G, 0) and [S, S + G) <- src row reflect(t) = -t resp.
+ * 2 (S - 1) - t (reflect = 1, needs S > G: F.pad(mode="reflect")) or zeros (reflect = 0: in front of a transposed convolution).
+ * interior = 1 copies rows [0, S) too (src and dst are different buffers); interior = 0 writes the 2G guard rows only (in place:
+ * src = dst + G * ld_dst). */
+int fs2_melgan_guard_rows(const void* src, long ld_src, long src_bstride, void* dst, long ld_dst, long dst_bstride, int B, int S,
+                          int G, int C, int reflect, int interior, int dtype, fs2_stream_t stream);
+/* The three ResnetBlocks of a narrow up-sampling stage (C = 32 / 64, bf16) in ONE launch:
+ *   for d in (d0, d1, d2):  x = shortcut(x) + conv4(lrelu(conv3(reflect_pad_d(lrelu(x)), dilation d)))       (k = 3, 1, 1; lrelu slope)
+ * x / y: row t of item b at base + b * bstride + t * ld (elements); reflection at the ends of [0, S) of every item.
+ * w: [3][5C][C] (per block: conv3 tap 0, 1, 2 as [cout][cin], shortcut, conv4), bias: [3][2][C] f32 (conv3's; shortcut's + conv4's).
+ * y = leaky_relu(result, out_slope) when out_slope > 0.  x is read once, y written once; S >= 32, dilations <= 9.
+ * fs2_melgan_stage_supported: 1 when (C, dtype) has an instantiation (a flag, not a status) - otherwise run the convolutions one by one. */
+int fs2_melgan_stage_supported(int C, int dtype);
+int fs2_melgan_stage_fwd(const void* x, long ldx, long x_bstride, const void* w, const float* bias, void* y, long ldy, long y_bstride,
+                         float slope, float out_slope, int B, int S, int C, int d0, int d1, int d2, int dtype, fs2_stream_t stream);
 /* stft.py:60-66: xp[b][i] = y[b][reflect(i - P)], i < N + 2P; zero-filled up to row_len. */
 int fs2_reflect_pad(const float* y, float* xp, int B, int N, int P, long row_len, fs2_stream_t stream);
 /* The same for a ragged batch (preprocessor/preprocessor.py:194 over a corpus): row b holds lens[b] samples (row stride ldy,

@@ -92,6 +92,9 @@ def parse_args(argv=None):
     parser.add_argument("--hw_queues", type=int, default=fastspeech2_amd.HW_QUEUES_DEFAULT,
                         help="HIP hardware queues of this process (GPU_MAX_HW_QUEUES; the runtime default 4 makes streams share queues: "
                              "utils.SynthPipeline / the engine's side streams); the same for every world size; an exported value wins; 0 = leave the runtime default")
+    parser.add_argument("--melgan_dir", default="melgan",
+                        help="vocoder.model MelGAN: directory with linda_johnson.pt / multi_speaker.pt (after a torch.hub run of the "
+                             "reference they lie in ~/.cache/torch/hub/descriptinc_melgan-neurips_master/models/)")
     parser.add_argument("--random_vocoder", action="store_true", help="allow a random-init vocoder when no checkpoint exists (smoke runs)")
     parser.add_argument("--griffin_iters", type=int, default=0,
                         help="N > 0: waveforms by N Griffin-Lim iterations on the post-net mel (float32 wavs, no vocoder loaded); 0 = HiFi-GAN")
@@ -110,7 +113,7 @@ def main(args):
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     device = torch.device("cuda", torch.cuda.current_device())
     model = get_model(args, configs, device, train=False, compute_dtype=args.dtype)
-    vocoder = None if args.griffin_iters > 0 else get_vocoder(model_config, device, hifigan_dir=args.hifigan_dir,
+    vocoder = None if args.griffin_iters > 0 else get_vocoder(model_config, device, hifigan_dir=args.hifigan_dir, melgan_dir=args.melgan_dir,
                                                               compute_dtype=args.vocoder_dtype, allow_random_init=args.random_vocoder)
     if args.mode == "batch":
         dataset = TextDataset(args.source, preprocess_config)

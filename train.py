@@ -73,7 +73,7 @@ def main(args, configs):
     vocoder = None
     if main_rank and not args.no_vocoder:
         try:
-            vocoder = get_vocoder(model_config, device, hifigan_dir=args.hifigan_dir)
+            vocoder = get_vocoder(model_config, device, hifigan_dir=args.hifigan_dir, melgan_dir=args.melgan_dir)
         except (FileNotFoundError, NotImplementedError) as e:
             print(f"[train] vocoder unavailable ({e}); audio samples are skipped")
 
@@ -155,6 +155,7 @@ def parse_args(argv=None):
     parser.add_argument("--dtype", default=None, choices=[None, "fp32", "bf16"],
                         help="compute dtype of the HIP engine (default: FS2_DTYPE or fp32; master weights are always fp32)")
     parser.add_argument("--hifigan_dir", default="hifigan")
+    parser.add_argument("--melgan_dir", default="melgan", help="vocoder.model MelGAN: directory with linda_johnson.pt / multi_speaker.pt")
     parser.add_argument("--group_size", type=int, default=4, help="sorting window of the batch sampler in batches (reference train.py:31: 4)")
     parser.add_argument("--hw_queues", type=int, default=fastspeech2_amd.HW_QUEUES_DEFAULT,
                         help="HIP hardware queues of this process (GPU_MAX_HW_QUEUES; the runtime default 4 makes streams share queues: "
