@@ -21,6 +21,8 @@
 //                      tail of the pair's rows; the wave then moves it to the front, so the path reads from (0, 0)
 //   fs2_dtw_f0         per pair the V/UV mismatches, the both-voiced count and the squared cents along the path, each lane over
 //                      k = lane, lane + 256, ... ascending, then a fixed tree
+//   fs2_dtw_prosody    per pair the gross pitch errors, the central sums of ln F0 on both sides (mean first, then a second pass) and
+//                      the absolute energy differences along the path, summed like fs2_dtw_f0
 #include "fs2_common.h"
 
 #define DT_MAX_FRAMES 2048          // two rows per lane of the largest workgroup
@@ -355,5 +357,105 @@ extern "C" int fs2_dtw_f0(const int32_t* pi, const int32_t* pj, long ldq, const 
     if (B == 0) return FS2_OK;
     dtw_f0_kernel<<<B, 256, 0, stream>>>(pi, pj, ldq, plen, f0_ref, ldr, f0_syn, lds, alens, blens, sums, ldo, T1max, T2max);
     FS2_CHECK_LAUNCH("dtw_f0");
+    return FS2_OK;
+}
+
+// ------------------------------------------------------------------ prosody along the path
+// Over the path cells with r = f0_ref[pi[k]], s = f0_syn[pj[k]], V the cells with r > 0 and s > 0, x = ln r, y = ln s over V, and
+// er = e_ref[pi[k]], es = e_syn[pj[k]] (float32 promoted):
+//   sums[p] = {gross = cells of V with fabs(s - r) > 0.2 r, n = |V|, cells where exactly one of r, s is 0,
+//              Sxx = sum (x - xm)^2, Syy = sum (y - ym)^2, Sxy = sum (x - xm)(y - ym), sum |er - es|, sum er}
+// with xm = (sum x) / n and ym = (sum y) / n from a first pass; the second pass evaluates the logarithms again rather than keep up
+// to 4095 pairs of them.  The comparison is one subtraction and one product, unfused.  A path entry outside the pair is skipped.
+#define DT_PROSODY_SUMS 8
+static __device__ __forceinline__ void dt_tree(double (*red)[256], int rows, int tid) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {                                   // fixed tree: the same sums on every run
+        if (tid < o)
+            for (int q = 0; q < rows; ++q) red[q][tid] += red[q][tid + o];
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(256) dtw_prosody_kernel(const int32_t* __restrict__ pi, const int32_t* __restrict__ pj, long ldq,
+                                                          const int32_t* __restrict__ plen, const double* __restrict__ f0r, long ldr,
+                                                          const double* __restrict__ f0s, long lds, const float* __restrict__ er,
+                                                          long lder, const float* __restrict__ es, long ldes,
+                                                          const int32_t* __restrict__ alens, const int32_t* __restrict__ blens,
+                                                          double* __restrict__ sums, long ldo, int T1max, int T2max) {
+#pragma clang fp contract(off)
+    __shared__ double red[7][256];
+    const int p = blockIdx.x, tid = threadIdx.x, T1 = dt_len(alens, p, T1max), T2 = dt_len(blens, p, T2max);
+    const int P = (int)min((long)max(plen[p], 0), ldq);
+    const int32_t* qi = pi + (size_t)p * ldq;
+    const int32_t* qj = pj + (size_t)p * ldq;
+    const double* fr = f0r + (size_t)p * ldr;
+    const double* fs = f0s + (size_t)p * lds;
+    const float* pr = er + (size_t)p * lder;
+    const float* ps = es + (size_t)p * ldes;
+    double gross = 0.0, voiced = 0.0, mism = 0.0, sx = 0.0, sy = 0.0, de = 0.0, se = 0.0;
+    for (int k = tid; k < P; k += 256) {
+        const int i = qi[k], j = qj[k];
+        if (i < 0 || i >= T1 || j < 0 || j >= T2) continue;
+        const double r = fr[i], s = fs[j], a = (double)pr[i], b = (double)ps[j];
+        if ((r == 0.0) != (s == 0.0)) mism += 1.0;
+        if (r > 0.0 && s > 0.0) {
+            const double diff = s - r, bound = 0.2 * r;
+            if (fabs(diff) > bound) gross += 1.0;
+            voiced += 1.0;
+            sx += log(r);
+            sy += log(s);
+        }
+        de += fabs(a - b);
+        se += a;
+    }
+    red[0][tid] = gross;
+    red[1][tid] = voiced;
+    red[2][tid] = mism;
+    red[3][tid] = sx;
+    red[4][tid] = sy;
+    red[5][tid] = de;
+    red[6][tid] = se;
+    dt_tree(red, 7, tid);
+    const double n = red[1][0];
+    const double xm = n > 0.0 ? red[3][0] / n : 0.0, ym = n > 0.0 ? red[4][0] / n : 0.0;
+    double* o = sums + (size_t)p * ldo;
+    if (tid == 0) {
+        o[0] = red[0][0];
+        o[1] = n;
+        o[2] = red[2][0];
+        o[6] = red[5][0];
+        o[7] = red[6][0];
+    }
+    __syncthreads();                                                       // everyone has read the means before red is reused
+    double sxx = 0.0, syy = 0.0, sxy = 0.0;
+    for (int k = tid; k < P; k += 256) {
+        const int i = qi[k], j = qj[k];
+        if (i < 0 || i >= T1 || j < 0 || j >= T2) continue;
+        const double r = fr[i], s = fs[j];
+        if (r > 0.0 && s > 0.0) {
+            const double dx = log(r) - xm, dy = log(s) - ym;
+            sxx += dx * dx;
+            syy += dy * dy;
+            sxy += dx * dy;
+        }
+    }
+    red[0][tid] = sxx;
+    red[1][tid] = syy;
+    red[2][tid] = sxy;
+    dt_tree(red, 3, tid);
+    if (tid < 3) o[3 + tid] = red[tid][0];
+}
+extern "C" int fs2_dtw_prosody(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* plen, const double* f0_ref, long ldr,
+                               const double* f0_syn, long lds, const float* e_ref, long lder, const float* e_syn, long ldes,
+                               const int32_t* alens, const int32_t* blens, double* sums, long ldo, int B, int T1max, int T2max,
+                               hipStream_t stream) {
+    FS2_CHECK_ARG(pi && pj && plen && f0_ref && f0_syn && e_ref && e_syn && alens && blens && sums, "dtw_prosody: null pointer");
+    DT_PAIR_ARGS("dtw_prosody");
+    FS2_CHECK_ARG(ldq >= 0 && ldr >= T1max && lds >= T2max && lder >= T1max && ldes >= T2max && ldo >= DT_PROSODY_SUMS,
+                  "dtw_prosody: bad strides path %ld f0 %ld %ld energy %ld %ld sums %ld", ldq, ldr, lds, lder, ldes, ldo);
+    if (B == 0) return FS2_OK;
+    dtw_prosody_kernel<<<B, 256, 0, stream>>>(pi, pj, ldq, plen, f0_ref, ldr, f0_syn, lds, e_ref, lder, e_syn, ldes, alens, blens, sums,
+                                              ldo, T1max, T2max);
+    FS2_CHECK_LAUNCH("dtw_prosody");
     return FS2_OK;
 }

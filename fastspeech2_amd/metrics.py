@@ -34,6 +34,41 @@ Corpus summary (`summarize`).  For mcd_db, f0_rmse_cents and vuv_error the mean 
 path_len (F0: over the utterances whose value is not NaN, weighted by n_voiced_pairs), and the number of utterances whose F0 score
 is NaN.
 
+Prosody (`prosody=True`, `score.py --prosody`; needs F0).  The numbers FastSpeech 2 reports for its variance adaptor: the moments of
+the voiced F0 and the DTW distance between the pitch contours (its Table 3), the error of the frame energy (Table 4), and the
+pitch-tracking error rates usually printed next to F0 RMSE.  The paper states neither how it treats unvoiced frames nor the unit of
+its DTW distance: voiced-only contours in Hz, a distance normalised by the path length and energy in the preprocessor's
+un-normalised units are this tool's choices, so the numbers compare runs of this tool and only roughly compare with the paper's.
+All arithmetic is float64, sums are in a fixed order without atomics, padding is never read or written, two runs are byte-identical.
+  On the path (`prosody_on_path`, kernel fs2_dtw_prosody).  The pair's path has P cells (i, j); r = f0_ref[i], s = f0_syn[j]; V is
+  the set of cells with r > 0 and s > 0, n = |V| = n_voiced_pairs; e is the float32 STFT energy `mel_spectrogram_ragged` returns for
+  the clamped audio (the L2 norm of the magnitudes of a frame, what `Preprocessor` extracts), cut to the pair's frame counts and
+  promoted to float64.
+    gross          the number of V cells with fabs(s - r) > 0.2 * r, evaluated as written: one subtraction, one product, nothing fused
+    gpe            gross / n, NaN when n = 0
+    ffe            (gross + V/UV mismatches) / P
+    f0_corr        with x = ln r, y = ln s over V: xm = (sum x) / n, ym = (sum y) / n in a first pass, then Sxx = sum (x - xm)^2,
+                   Syy = sum (y - ym)^2, Sxy = sum (x - xm)(y - ym); f0_corr = Sxy / sqrt(Sxx Syy), NaN when n < 2 or one of
+                   Sxx, Syy <= 1e-24 n.  That floor is a standard deviation of ln F0 below 1e-12, a constant track: the rounding of
+                   the mean alone leaves about 1e-29 per term, and no real track comes near 1e-12.
+    energy_mae     sum |e_ref[i] - e_syn[j]| / P
+    energy_mae_rel sum |e_ref[i] - e_syn[j]| / sum e_ref[i] over the same cells, NaN when that denominator is 0
+  Per side, off the path (`voiced_contours`, kernel fs2_prosody_voiced).  The frames with f0 > 0 among the side's T frames, in order,
+  are the contour u of n_v values in Hz.  Its mean um = (sum u) / n_v, then in a second pass M2 = sum (u - um)^2, M3 = sum (u - um)^3,
+  M4 = sum (u - um)^4; with n_v = 0 all four are 0.  Rows carry them as f0_stats_ref / f0_stats_syn = {n, mean, m2, m3, m4}.
+  Pitch-contour DTW (`contour_dtw`).  The recurrence, tie rule and kernels above with K = 1 on the two contours u (n_r values) and w
+  (n_s values): the local cost sqrt((u - w)^2) is |u - w|.  f0_dtw_hz = D(n_r - 1, n_s - 1) / P', P' that path's length, reported as
+  f0_dtw_path_len; NaN and 0 when a side has no voiced frame (such a pair is left out of the launch).  It runs after the cepstral
+  DTW's cost and backpointer buffers are released and is no larger, n_v <= T.
+  Summary.  For gpe, ffe, f0_corr, f0_dtw_hz, energy_mae and energy_mae_rel the mean and the weighted mean over the utterances whose
+  value is not NaN (gpe and f0_corr weighted by n, ffe and the energy errors by P, f0_dtw_hz by P') and the number of NaN utterances
+  (`<key>_nan_utterances`).  Corpus pitch moments per side: the per-utterance (n, mean, M2, M3, M4) merged pairwise in row order by
+  Pebay's update formulas (`merge_moments`), then sigma = sqrt(M2 / N), gamma = (M3 / N) / sigma^3, K = (M4 / N) / sigma^4 - 3:
+  population moments, excess kurtosis (the paper's K of about 1 for natural speech is an excess value), as f0_std_hz_ref,
+  f0_skew_ref, f0_kurt_ref, the `_syn` three and the voiced frames N as f0_voiced_frames_ref / _syn; NaN where N = 0 (the skewness
+  and kurtosis also where sigma = 0).
+Without `prosody` every row and every summary key is what it is without this section.
+
 Storage.  The local costs and backpointers of a pair are held skewed, cell (i, j) at row (i + j) mod T2, column i of a (T2max, T1max)
 matrix: an anti-diagonal is contiguous, the buffer is no larger than the plain one (`unskew` undoes it for a test).  The accumulated
 costs never leave the chip.  Determinism: no atomics, sums in a fixed order; two runs give byte-identical scores.
@@ -50,6 +85,10 @@ WHO = "fastspeech2_amd.metrics"
 MAX_FRAMES, MAX_MCEP, MAX_MEL = 2048, 40, 128
 MCD_SCALE = 10.0 / math.log(10.0) * math.sqrt(2.0)
 CELL_BYTES = 9                                              # one float64 local cost and one backpointer byte per (i, j)
+PROSODY_SUMS = 8                                            # gross, n, V/UV mismatches, Sxx, Syy, Sxy, sum |de|, sum e_ref
+PROSODY_FRAME_BYTES = 24                                    # per frame: the compacted contour (8 B) and its share of the second path
+CORR_FLOOR = 1e-24
+PROSODY_SCORES = ("gpe", "ffe", "f0_corr", "f0_dtw_hz", "energy_mae", "energy_mae_rel")
 
 
 def max_frames():
@@ -213,6 +252,89 @@ def f0_on_path(pi, pj, path_len, f0_ref, alens, f0_syn, blens, out=None):
     return sums
 
 
+def _on_device(t, dtype, what, dim):
+    """`_dev` for the prosody entry points, which refuse a host tensor like every other bad argument: a ValueError."""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise ValueError(f"{what} must be a tensor on the GPU ({WHO} has no CPU fallback)")
+    return _dev(t, dtype, what, dim)
+
+
+def voiced_contours(f0, lens, out=None):
+    """F0 tracks f0 (B, >= Tmax) float64 on the device, lens frames per row -> (contour (B, Tmax) float64 holding row b's voiced
+    frames, in order, in [b, :n_v[b]] and nothing written beyond, n_v (B,) int32, stats (B, 5) float64 = n_v, mean, M2, M3, M4),
+    all on the device.  `out` is a caller's contour buffer, any row stride."""
+    lens_h = _host_lens(lens)
+    for n in lens_h:
+        if n > MAX_FRAMES:
+            raise ValueError(f"a sequence of {n} frames is outside the supported 0..{MAX_FRAMES} frames")
+    f0 = _on_device(f0, torch.float64, "f0", 2)
+    B = f0.shape[0]
+    _, lens_d = ragged.lengths(lens_h, B, f0.shape[1], "lens", f0.device)
+    Tmax = max(lens_h, default=0)
+    contour = _out(out, (B, Tmax), torch.float64, "out", f0.device)
+    n_v = torch.empty(B, dtype=torch.int32, device=f0.device)
+    stats = torch.empty(B, 5, dtype=torch.float64, device=f0.device)
+    _lib.call("fs2_prosody_voiced", f0.data_ptr(), f0.stride(0), lens_d.data_ptr(), contour.data_ptr(), contour.stride(0),
+              n_v.data_ptr(), stats.data_ptr(), stats.stride(0), B, Tmax, ops._stream())
+    return contour, n_v, stats
+
+
+def prosody_on_path(pi, pj, path_len, f0_ref, alens, f0_syn, blens, e_ref, e_syn, out=None):
+    """Path and F0 tracks as `f0_on_path` takes them, frame energies e_ref (B, >= T1max), e_syn (B, >= T2max) float32 on the device
+    -> sums (B, 8) float64: gross pitch errors, both-voiced cells n, V/UV mismatches, Sxx, Syy, Sxy of ln F0 over the both-voiced
+    cells, sum |e_ref - e_syn|, sum e_ref (module docstring)."""
+    ah, bh, T1, T2 = _pair_lens(alens, blens)
+    pi, pj = _on_device(pi, torch.int32, "pi", 2), _on_device(pj, torch.int32, "pj", 2)
+    f0_ref, f0_syn = _on_device(f0_ref, torch.float64, "f0_ref", 2), _on_device(f0_syn, torch.float64, "f0_syn", 2)
+    e_ref, e_syn = _on_device(e_ref, torch.float32, "e_ref", 2), _on_device(e_syn, torch.float32, "e_syn", 2)
+    path_len = _on_device(path_len, torch.int32, "path_len", 1)
+    B = pi.shape[0]
+    ad, bd = _lens_dev(ah, bh, B, pi.device)
+    if pj.shape != pi.shape or pi.stride(0) != pj.stride(0) or any(t.shape[0] != B for t in (path_len, f0_ref, f0_syn, e_ref, e_syn)) \
+            or min(f0_ref.shape[1], e_ref.shape[1]) < T1 or min(f0_syn.shape[1], e_syn.shape[1]) < T2:
+        raise ValueError(f"path {tuple(pi.shape)} {tuple(pj.shape)}, f0 {tuple(f0_ref.shape)} {tuple(f0_syn.shape)}, energy "
+                         f"{tuple(e_ref.shape)} {tuple(e_syn.shape)} and the lengths do not fit together")
+    sums = _out(out, (B, PROSODY_SUMS), torch.float64, "out", pi.device)
+    _lib.call("fs2_dtw_prosody", pi.data_ptr(), pj.data_ptr(), pi.stride(0), path_len.data_ptr(), f0_ref.data_ptr(), f0_ref.stride(0),
+              f0_syn.data_ptr(), f0_syn.stride(0), e_ref.data_ptr(), e_ref.stride(0), e_syn.data_ptr(), e_syn.stride(0),
+              ad.data_ptr(), bd.data_ptr(), sums.data_ptr(), sums.stride(0), B, T1, T2, ops._stream())
+    return sums
+
+
+def contour_dtw(u, n_ref, w, n_syn):
+    """Compacted contours u (B, >= max n_ref), w (B, >= max n_syn) float64 on the device and their voiced counts on the host ->
+    (total (B,) float64 = D(n_r - 1, n_s - 1), path_len (B,) int32, pi, pj (B, L) int32, launched): `dtw` with K = 1 over the pairs
+    whose two sides both have a voiced frame, whose indices are `launched`; the others get NaN, 0 and -1 and reach no kernel."""
+    nr, ns = _host_lens(n_ref), _host_lens(n_syn)
+    for n in nr + ns:
+        if not 0 <= n <= MAX_FRAMES:
+            raise ValueError(f"a contour of {n} frames is outside the supported 0..{MAX_FRAMES} frames")
+    u, w = _on_device(u, torch.float64, "u", 2), _on_device(w, torch.float64, "w", 2)
+    B = u.shape[0]
+    if w.shape[0] != B:
+        raise ValueError(f"u {tuple(u.shape)} and w {tuple(w.shape)} are not B pairs of contours")
+    ragged.lengths(nr, B, u.shape[1], "n_ref")
+    ragged.lengths(ns, B, w.shape[1], "n_syn")
+    launched = [p for p in range(B) if nr[p] > 0 and ns[p] > 0]
+    T1, T2 = max((nr[p] for p in launched), default=1), max((ns[p] for p in launched), default=1)
+    L = T1 + T2 - 1
+    total = torch.full((B,), float("nan"), dtype=torch.float64, device=u.device)
+    plen = torch.zeros(B, dtype=torch.int32, device=u.device)
+    pi = torch.full((B, L), -1, dtype=torch.int32, device=u.device)
+    pj = torch.full((B, L), -1, dtype=torch.int32, device=u.device)
+    if launched:
+        sel = torch.tensor(launched, dtype=torch.int64, device=u.device)
+        a, b = u.index_select(0, sel)[:, :T1].unsqueeze(2), w.index_select(0, sel)[:, :T2].unsqueeze(2)
+        la, lb = [nr[p] for p in launched], [ns[p] for p in launched]
+        cost = local_cost(a, la, b, lb)
+        bp, t = scan(cost, la, lb)
+        del cost
+        qi, qj = pi[:len(launched)].clone(), pj[:len(launched)].clone()      # -1 everywhere: backtrack leaves a row's tail alone
+        n, qi, qj = backtrack(bp, la, lb, out=(qi, qj))
+        total[sel], plen[sel], pi[sel], pj[sel] = t, n, qi, qj
+    return total, plen, pi, pj, launched
+
+
 def unskew(m, alens, blens, fill):
     """Skewed (B, T2max, T1max) numpy array -> plain (B, T1max, T2max) with `fill` outside each pair (for tests and debugging)."""
     m = np.asarray(m)
@@ -236,6 +358,69 @@ def scores_from_sums(total, path_len, frames_ref, frames_syn, sums=None):
     return row
 
 
+def prosody_scores(sums, path_len, stats_ref, stats_syn, contour_total, contour_len):
+    """The prosody keys of a pair's row (module docstring) from the device results copied to the host: the 8 path sums, the 5
+    per-side statistics and the pitch-contour DTW's total and path length."""
+    nan = float("nan")
+    P, gross, n, mism = int(path_len), int(sums[0]), int(sums[1]), int(sums[2])
+    sxx, syy, sxy, de, se = (float(v) for v in sums[3:8])
+    corr_ok = n >= 2 and sxx > CORR_FLOOR * n and syy > CORR_FLOOR * n
+    Pc = int(contour_len)
+    stat = lambda q: {"n": int(q[0]), "mean": float(q[1]), "m2": float(q[2]), "m3": float(q[3]), "m4": float(q[4])}   # noqa: E731
+    return {"gpe": gross / n if n else nan, "ffe": (gross + mism) / P, "f0_corr": sxy / math.sqrt(sxx * syy) if corr_ok else nan,
+            "f0_dtw_hz": float(contour_total) / Pc if Pc else nan, "f0_dtw_path_len": Pc, "energy_mae": de / P,
+            "energy_mae_rel": de / se if se != 0.0 else nan, "f0_stats_ref": stat(stats_ref), "f0_stats_syn": stat(stats_syn)}
+
+
+def merge_moments(a, b):
+    """(n, mean, M2, M3, M4) of two disjoint sets -> those of their union (Pebay's pairwise update formulas), in float64."""
+    na, ma, a2, a3, a4 = a
+    nb, mb, b2, b3, b4 = b
+    if na == 0:
+        return b
+    if nb == 0:
+        return a
+    n = na + nb
+    d = mb - ma
+    m2 = a2 + b2 + d * d * na * nb / n
+    m3 = a3 + b3 + d ** 3 * na * nb * (na - nb) / n ** 2 + 3.0 * d * (na * b2 - nb * a2) / n
+    m4 = a4 + b4 + d ** 4 * na * nb * (na * na - na * nb + nb * nb) / n ** 3 + 6.0 * d * d * (na * na * b2 + nb * nb * a2) / n ** 2 \
+        + 4.0 * d * (na * b3 - nb * a3) / n
+    return n, ma + d * nb / n, m2, m3, m4
+
+
+def corpus_moments(stats):
+    """Per-utterance {n, mean, m2, m3, m4} dicts, merged in the order given -> (N, sigma, skewness, excess kurtosis); NaN without
+    a voiced frame, the last two also when sigma = 0."""
+    acc = (0, 0.0, 0.0, 0.0, 0.0)
+    for q in stats:
+        acc = merge_moments(acc, (int(q["n"]), float(q["mean"]), float(q["m2"]), float(q["m3"]), float(q["m4"])))
+    N, _, m2, m3, m4 = acc
+    nan = float("nan")
+    if N == 0:
+        return 0, nan, nan, nan
+    sigma = math.sqrt(m2 / N)
+    if sigma == 0.0:
+        return N, 0.0, nan, nan
+    return N, sigma, (m3 / N) / sigma ** 3, (m4 / N) / sigma ** 4 - 3.0
+
+
+def _summarize_prosody(rows, out):
+    weights = {"gpe": "n_voiced_pairs", "f0_corr": "n_voiced_pairs", "ffe": "path_len", "energy_mae": "path_len",
+               "energy_mae_rel": "path_len", "f0_dtw_hz": "f0_dtw_path_len"}
+    for key in PROSODY_SCORES:
+        v = np.array([r[key] for r in rows], np.float64)
+        w = np.array([r[weights[key]] for r in rows], np.float64)
+        ok = ~np.isnan(v)
+        out[key + "_mean"] = float(v[ok].mean()) if ok.any() else float("nan")
+        out[key + "_weighted"] = float((v[ok] * w[ok]).sum() / w[ok].sum()) if ok.any() and w[ok].sum() > 0 else float("nan")
+        out[key + "_nan_utterances"] = int((~ok).sum())
+    for side in ("ref", "syn"):
+        N, sigma, skew, kurt = corpus_moments([r["f0_stats_" + side] for r in rows])
+        out["f0_voiced_frames_" + side], out["f0_std_hz_" + side] = N, sigma
+        out["f0_skew_" + side], out["f0_kurt_" + side] = skew, kurt
+
+
 def summarize(rows):
     """Corpus summary of per-utterance score dicts (module docstring)."""
     out = {"utterances": len(rows)}
@@ -255,14 +440,18 @@ def summarize(rows):
         out["f0_rmse_cents_mean"] = float(f0[ok].mean()) if ok.any() else float("nan")
         out["f0_rmse_cents_weighted"] = float((f0[ok] * nv[ok]).sum() / nv[ok].sum()) if ok.any() else float("nan")
         out["f0_nan_utterances"] = int((~ok).sum())
+    if "gpe" in rows[0]:
+        _summarize_prosody(rows, out)
     return out
 
 
-def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0):
+def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0, prosody=False):
     """What a batch of n pairs padded to (T1, T2) frames holds on the device: 9 B per (i, j) cell (local cost + backpointer), the
     audio, its STFT workspace and mel (about 40 B per sample), cepstra, F0 and the path; with `fft_size` (cepstra="world") also the
-    spectral envelope, fft_size / 2 + 1 float64 bins per frame and side."""
-    return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64 + (fft_size // 2 + 1) * 8 * (fft_size > 0)))
+    spectral envelope, fft_size / 2 + 1 float64 bins per frame and side; with `prosody` the compacted contours and the second path
+    (24 B per frame; the contour DTW's cells reuse the first DTW's, released by then)."""
+    return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64 + (fft_size // 2 + 1) * 8 * (fft_size > 0)
+                                                    + PROSODY_FRAME_BYTES * bool(prosody)))
 
 
 def load_audio(path, sampling_rate):
@@ -283,15 +472,22 @@ def frame_counts(n_samples, sampling_rate, hop_length, f0=True):
 
 
 def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None, f0=True, device="cuda", budget=4 << 30,
-                cepstra="mel", alpha=None):
+                cepstra="mel", alpha=None, prosody=False):
     """Scores of (recorded, synthesized) pairs of float32 waveforms at `sampling_rate` -> one dict per pair (module docstring), in
     the order given.  `stft` is the config's `audio.TacotronSTFT`.  Pairs are packed longest first into ragged batches under `budget`
     bytes of device buffers; per batch: both sides through one pinned staging buffer, mel -> cepstra -> local cost -> scan ->
     backtrack (and DIO + StoneMask -> the path sums with `f0`), one D2H copy of the scores.  With cepstra="world" the cepstra are
     `envelope.world_cepstra` (n_mcep 24 by default, all-pass constant `alpha` or the table's) of the unclamped audio at its DIO +
     StoneMask F0, which is then always extracted, on DIO's frame grid, and only reported with `f0`; no mel is taken and `stft` may
-    be None.  Every row then also carries cepstra, alpha and fft_size."""
+    be None.  Every row then also carries cepstra, alpha and fft_size.  With `prosody` (needs `f0` and the STFT) every row also
+    carries the prosody keys of the module docstring: the STFT's frame energy is kept (with cepstra="world" the STFT is run on the
+    clamped audio for it alone), both F0 tracks are compacted, with one D2H copy of the voiced counts per side, and the
+    pitch-contour DTW runs once the cepstral DTW's buffers are released."""
     from . import envelope as Env
+    if prosody and not f0:
+        raise ValueError("prosody scores need F0: prosody=True cannot go with f0=False")
+    if prosody and stft is None:
+        raise ValueError("prosody scores need the STFT for the frame energy: stft=None cannot go with prosody=True")
     if cepstra not in ("mel", "world"):
         raise ValueError(f"cepstra must be 'mel' or 'world', got {cepstra!r}")
     world = cepstra == "world"
@@ -314,7 +510,7 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
     fr = [frame_counts(len(w), sampling_rate, hop_length, f0 or world) for w in ref_wavs]
     fs = [frame_counts(len(w), sampling_rate, hop_length, f0 or world) for w in syn_wavs]
     check_frames(fr, fs)
-    short = [] if world else [len(w) for w in list(ref_wavs) + list(syn_wavs) if len(w) <= stft.filter_length // 2]
+    short = [] if world and not prosody else [len(w) for w in list(ref_wavs) + list(syn_wavs) if len(w) <= stft.filter_length // 2]
     if short:
         raise ValueError(f"a waveform of {short[0]} samples is too short for the STFT's reflect padding ({stft.filter_length // 2})")
     dev = ragged.require_device(torch.device(device), WHO)
@@ -331,23 +527,36 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
             from . import pitch as Pitch
             f, _, f_frames = Pitch.dio(y, lens, sampling_rate, frame_period)
             track = Pitch.stonemask(y, lens, f, f_frames, sampling_rate, frame_period)
+        mel = energy = None
+        if prosody or not world:
+            mel, energy, _ = stft.mel_spectrogram_ragged(y.clamp(-1.0, 1.0), lens)
         if world:
-            return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), track if f0 else None
-        mel, _, _ = stft.mel_spectrogram_ragged(y.clamp(-1.0, 1.0), lens)
-        return cepstra_fn(mel, frames, n_mcep), track
+            return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), track if f0 else None, energy
+        return cepstra_fn(mel, frames, n_mcep), track, energy
 
-    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size)     # noqa: E731
+    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody)     # noqa: E731
     for batch in ragged.greedy_batches(list(zip(fr, fs)), budget, cost):
         al, bl = [fr[i] for i in batch], [fs[i] for i in batch]
-        a, f0a = side([ref_wavs[i] for i in batch], al)
-        b, f0b = side([syn_wavs[i] for i in batch], bl)
+        a, f0a, ea = side([ref_wavs[i] for i in batch], al)
+        b, f0b, eb = side([syn_wavs[i] for i in batch], bl)
         total, plen, pi, pj = dtw(a, al, b, bl)
+        del a, b
         cols = [total, plen.to(torch.float64)]
         if f0:
             cols += list(f0_on_path(pi, pj, plen, f0a, al, f0b, bl).unbind(1))
-        host = torch.stack(cols, dim=1).cpu().numpy()                       # the batch's one D2H copy
+        if prosody:
+            cols += list(prosody_on_path(pi, pj, plen, f0a, al, f0b, bl, ea, eb).unbind(1))
+            del pi, pj
+            u, nu, su = voiced_contours(f0a, al)
+            w, nw, sw = voiced_contours(f0b, bl)
+            ctotal, cplen, _, _, _ = contour_dtw(u, nu.cpu(), w, nw.cpu())    # the voiced counts: one small D2H copy per side
+            cols += list(su.unbind(1)) + list(sw.unbind(1)) + [ctotal, cplen.to(torch.float64)]
+        host = torch.stack(cols, dim=1).cpu().numpy()                       # the batch's one D2H copy of the scores
         for r, i in enumerate(batch):
             rows[i] = scores_from_sums(host[r, 0], host[r, 1], al[r], bl[r], host[r, 2:5] if f0 else None)
+            if prosody:
+                q = host[r, 5:]
+                rows[i].update(prosody_scores(q[:8], host[r, 1], q[8:13], q[13:18], q[18], q[19]))
             if world:
                 rows[i].update(cepstra="world", alpha=alpha, fft_size=fft_size)
     return rows
@@ -408,13 +617,17 @@ class _Rates:
 
 
 def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=None, score_fn=None,
-        device="cuda", cepstra="mel", alpha=None):
+        device="cuda", cepstra="mel", alpha=None, prosody=False):
     """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
-    replaces the device stage.  Returns (rows, skipped, summary).  With cepstra="world" the rows and the summary also say cepstra,
-    alpha and fft_size; with "mel" they are what they were before that choice existed."""
+    replaces the device stage (called with `prosody=True` as a keyword when that is asked for).  Returns (rows, skipped, summary).
+    With cepstra="world" the rows and the summary also say cepstra, alpha and fft_size; with "mel" they are what they were before
+    that choice existed.  `prosody` adds the prosody keys of the module docstring and is refused with f0=False before a file is
+    read."""
     import json
     pp = config["preprocessing"]
     sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
+    if prosody and not f0:
+        raise ValueError("--prosody needs F0 and cannot go with --no_f0")
     world_keys = {}
     if cepstra == "world":                                                  # refused before a file is read
         from . import envelope as Env
@@ -428,7 +641,10 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
         stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], pp["mel"]["n_mel_channels"], sr,
                                   pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
         score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device, cepstra=cepstra,     # noqa: E731
-                                            alpha=alpha)
+                                            alpha=alpha, prosody=prosody)
+    elif prosody:
+        given = score_fn
+        score_fn = lambda r, s: given(r, s, prosody=True)                    # noqa: E731
     scores = score_fn([it["ref"] for it in items], [it["syn"] for it in items]) if items else []
     rows = [{"basename": it["basename"], "speaker": it["speaker"], "reference_window": it["window"], **sc}
             for it, sc in zip(items, scores)]

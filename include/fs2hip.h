@@ -460,6 +460,17 @@ int fs2_dtw_backtrack(const uint8_t* bp, long ldp_b, long ldp_s, const int32_t* 
 int fs2_dtw_f0(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* plen, const double* f0_ref, long ldr,
                const double* f0_syn, long lds, const int32_t* alens, const int32_t* blens, double* sums, long ldo, int B, int T1max,
                int T2max, fs2_stream_t stream);
+/* prosody along the path, with e_ref / e_syn [B][lde*] the float32 frame energies and V the cells with r > 0 and s > 0:
+ * sums[p][0..8) = {cells of V with fabs(s - r) > 0.2 r, |V|, cells where exactly one of r, s is 0, Sxx, Syy, Sxy of x = ln r and
+ * y = ln s over V about their means (mean first, then a second pass), sum |e_ref - e_syn|, sum e_ref}; ldo >= 8 */
+int fs2_dtw_prosody(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* plen, const double* f0_ref, long ldr,
+                    const double* f0_syn, long lds, const float* e_ref, long lder, const float* e_syn, long ldes, const int32_t* alens,
+                    const int32_t* blens, double* sums, long ldo, int B, int T1max, int T2max, fs2_stream_t stream);
+/* the voiced frames (f0 > 0) among the first lens[b] <= Tmax <= fs2_dtw_max_frames() of row b, in order, to out[b][0 .. nv[b]) (the
+ * rest of the row is left alone; out must not be f0), and stats[b][0..5) = {nv, mean, M2, M3, M4}, the central sums of those values
+ * about their mean in a second pass; all zero when nv[b] = 0.  Strides in elements: ldf, ldo >= Tmax, lds >= 5 */
+int fs2_prosody_voiced(const double* f0, long ldf, const int32_t* lens, double* out, long ldo, int32_t* nv, double* stats, long lds,
+                       int B, int Tmax, fs2_stream_t stream);
 
 /* ---- spectral envelope (CheapTrick) and its mel-cepstrum (specification: fastspeech2_amd/envelope.py) ----
  * fp64 throughout, ragged: row b has lens[b] samples of the float32 batch x (row stride ldx) and frames[b] frames (int32, device);

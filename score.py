@@ -2,7 +2,7 @@
 """score.py — objective scores of synthesized against recorded speech on the GPU (fastspeech2_amd/metrics.py):
 
     python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
-                    [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--out scores.jsonl]
+                    [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--out scores.jsonl]
 
 For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
 is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
@@ -12,7 +12,11 @@ output row says which was used.  One JSON object per utterance goes to `--out`, 
 (the default, 13 coefficients) the cepstra are a DCT of this project's own log-mel: the dB values compare runs of this tool, not
 published MCD figures.  With `--cepstra world` (24 coefficients) they are mel-cepstra of the CheapTrick spectral envelope, the
 published definition (fastspeech2_amd/envelope.py); the all-pass constant comes from the sampling rate unless `--alpha` gives it, and
-rows and summary also carry `cepstra`, `alpha` and `fft_size`.  Agreement with the pyworld / pysptk binaries is unmeasured."""
+rows and summary also carry `cepstra`, `alpha` and `fft_size`.  Agreement with the pyworld / pysptk binaries is unmeasured.
+With `--prosody` (not with `--no_f0`) every row and the summary also carry the numbers FastSpeech 2 evaluates its variance adaptor by:
+gross pitch error, F0 frame error and log-F0 correlation on the path, the DTW distance between the voiced pitch contours in Hz, the
+mean absolute error of the frame energy, and the standard deviation, skewness and excess kurtosis of the voiced F0 of both sides.
+The paper does not say how it treats unvoiced frames or in which unit its DTW distance is: these compare runs of this tool."""
 import argparse
 import json
 import sys
@@ -35,6 +39,8 @@ def parse_args(argv=None):
                         help="mel: DCT of the log-mel (tool-internal); world: mel-cepstra of the CheapTrick spectral envelope")
     parser.add_argument("--alpha", type=float, default=None, help="all-pass constant of --cepstra world (default: by sampling rate)")
     parser.add_argument("--n_mcep", type=int, default=None, help="cepstral coefficients 1..n_mcep (at most 40; default 13 mel, 24 world)")
+    parser.add_argument("--prosody", action="store_true",
+                        help="also GPE, FFE, log-F0 correlation, pitch-contour DTW, energy MAE and the pitch moments (needs F0)")
     parser.add_argument("--out", type=str, default="scores.jsonl")
     parser.add_argument("--device", type=str, default="cuda")
     return parser.parse_args(argv)
@@ -47,7 +53,8 @@ def main(argv=None, score_fn=None):
     try:
         rows, skipped, summary = metrics.run(config, train["path"]["result_path"], args.source, out_path=args.out, syn_dir=args.syn_dir,
                                              ref_dir=args.ref_dir, trim=not args.no_trim, f0=not args.no_f0, n_mcep=args.n_mcep,
-                                             score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha)
+                                             score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha,
+                                             prosody=args.prosody)
     except ValueError as e:
         sys.exit(str(e))
     for name, reason in skipped:

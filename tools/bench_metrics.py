@@ -9,6 +9,10 @@ One JSON line, all from one run on one box:
   host      the same pairs (local cost, DTW, backtrack, F0 sums) with the numpy oracle tests/dtw_ref.py over a pool of `--threads`
             processes (16 at most)
 
+  prosody   with `--prosody` also the kernels that switch adds: the path sums (fs2_dtw_prosody), the compaction and moments of both
+            sides (fs2_prosody_voiced) and the pitch-contour DTW (cost, scan and backtrack with K = 1 on the voiced frames, with the
+            D2H copy of the voiced counts it waits for), and their sum `prosody_ms` next to `batch_ms`
+
 There is no earlier implementation to compare with and no threshold: the numbers go to DESIGN.md."""
 import argparse
 import json
@@ -57,6 +61,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--host_pairs", type=int, default=256, help="pairs the host oracle runs (scaled to the batch)")
+    ap.add_argument("--prosody", action="store_true", help="also time what score.py --prosody adds")
     args = ap.parse_args()
     pairs = make_batch(args.pairs)
     al, bl = [len(p[0]) for p in pairs], [len(p[1]) for p in pairs]
@@ -109,6 +114,17 @@ def main():
     ms["scan"], (_, total) = timed(lambda: M.scan(cost, al, bl, out=bp))
     ms["backtrack"], (plen, pi, pj) = timed(lambda: M.backtrack(bp, al, bl))
     ms["f0"], sums = timed(lambda: M.f0_on_path(pi, pj, plen, f0a, al, f0b, bl))
+    extra = {}
+    if args.prosody:
+        ea, eb = torch.rand(B, T1, device=dev) * 40, torch.rand(B, T2, device=dev) * 40
+        pms = {}
+        pms["path_sums"], _ = timed(lambda: M.prosody_on_path(pi, pj, plen, f0a, al, f0b, bl, ea, eb))
+        pms["voiced"], ((u, nu, _), (w, nw, _)) = timed(lambda: (M.voiced_contours(f0a, al), M.voiced_contours(f0b, bl)))
+        pms["contour_dtw"], (_, cplen, _, _, launched) = timed(lambda: M.contour_dtw(u, nu.cpu(), w, nw.cpu()))
+        nu, nw = nu.cpu().numpy(), nw.cpu().numpy()
+        extra = {"prosody_ms_each": {k: round(v, 4) for k, v in pms.items()}, "prosody_ms": round(sum(pms.values()), 3),
+                 "contour_pairs": len(launched), "contour_cells": int((nu.astype(np.int64) * nw).sum()),
+                 "contour_path_len_max": int(cplen.max())}
     total, plen, sums = total.cpu().numpy(), plen.cpu().numpy(), sums.cpu().numpy()
     for k, i in enumerate(pick):                                             # the oracle's answers for the pairs it ran
         assert abs(total[i] - host[k][0]) <= 1e-6 * host[k][0] and plen[i] == host[k][1], (i, total[i], plen[i], host[k])
@@ -133,7 +149,7 @@ def main():
         "host_threads": min(args.threads, 16), "host_pairs_run": n_host, "host_seconds": round(t_host, 3),
         "host_pairs_per_s": round(B / t_host, 1),
         "gpu_dtw_ms": round(ms["cost"] + ms["scan"] + ms["backtrack"] + ms["f0"], 3),
-        "speedup_over_host": round(t_host * 1e3 / (ms["cost"] + ms["scan"] + ms["backtrack"] + ms["f0"]), 1)}), flush=True)
+        "speedup_over_host": round(t_host * 1e3 / (ms["cost"] + ms["scan"] + ms["backtrack"] + ms["f0"]), 1), **extra}), flush=True)
 
 
 if __name__ == "__main__":
