@@ -136,6 +136,9 @@ class Generator(nn.Module):
     def _pack_convt(layer, u, k, dev, cdt):
         """Polyphase pack of ConvTranspose1d(Cin, Cout, k, stride=u, padding=(k-u)//2):
         y[u*q + r, co] = sum_d sum_ci x[q + d, ci] * w[ci, co, r + p - u*d]  for the d with 0 <= r + p - u*d < k."""
+        if k < u or (k - u) % 2:
+            # padding (k - u) // 2 then gives (T - 1) u - 2 p + k != u T output samples: not the u-phase image built below
+            raise ValueError(f"ConvTranspose1d(k={k}, stride={u}): the polyphase pack needs k >= stride and k - stride even")
         w = layer.effective_weight().detach().to(dev, torch.float32)            # (Cin, Cout, k)
         cin, cout, _ = w.shape
         p = (k - u) // 2
