@@ -26,7 +26,8 @@ a ValueError before any launch.
 Scores per pair.  mcd_db = (10 / ln 10) sqrt(2) D(T1-1, T2-1) / P.  With r = f0_ref[i], s = f0_syn[j] over the P path cells (i, j):
 vuv_error = the share of cells where exactly one of r, s is 0;  f0_rmse_cents = sqrt(mean over the cells with r > 0 and s > 0 of
 (1200 log2(s / r))^2), NaN when there is no such cell; n_voiced_pairs is their number.  Also path_len = P, frames_ref = T1,
-frames_syn = T2.  F0 is DIO + StoneMask (`pitch`) with frame_period = hop / sampling_rate * 1000 as in `Preprocessor._extract_pitch`,
+frames_syn = T2.  F0 is DIO + StoneMask (`pitch`), or probabilistic YIN (`pyin`) with f0_estimator="pyin" (then every row says
+so), with frame_period = hop / sampling_rate * 1000 as in `Preprocessor._extract_pitch`,
 on the unclamped audio; the mel is taken of the audio clamped to [-1, 1].  F0 frame f and mel frame f are both centred at sample
 f * hop.  Where the two frame counts of an utterance differ (the last frame), both are cut to the smaller before the DTW.
 
@@ -472,7 +473,7 @@ def frame_counts(n_samples, sampling_rate, hop_length, f0=True):
 
 
 def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None, f0=True, device="cuda", budget=4 << 30,
-                cepstra="mel", alpha=None, prosody=False):
+                cepstra="mel", alpha=None, prosody=False, f0_estimator="dio"):
     """Scores of (recorded, synthesized) pairs of float32 waveforms at `sampling_rate` -> one dict per pair (module docstring), in
     the order given.  `stft` is the config's `audio.TacotronSTFT`.  Pairs are packed longest first into ragged batches under `budget`
     bytes of device buffers; per batch: both sides through one pinned staging buffer, mel -> cepstra -> local cost -> scan ->
@@ -482,8 +483,14 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
     be None.  Every row then also carries cepstra, alpha and fft_size.  With `prosody` (needs `f0` and the STFT) every row also
     carries the prosody keys of the module docstring: the STFT's frame energy is kept (with cepstra="world" the STFT is run on the
     clamped audio for it alone), both F0 tracks are compacted, with one D2H copy of the voiced counts per side, and the
-    pitch-contour DTW runs once the cepstral DTW's buffers are released."""
+    pitch-contour DTW runs once the cepstral DTW's buffers are released.  `f0_estimator` "pyin" takes the F0 track of both sides of
+    every F0 and prosody score from probabilistic YIN (`pyin`, the same frame grid) instead of DIO + StoneMask, and every row then
+    carries f0_estimator; with "dio" the rows are what they were before that choice existed.  CheapTrick (cepstra="world") keeps
+    its own DIO + StoneMask track whatever the estimator.  The pYIN workspace of a batch (`pyin.workspace_bytes`) counts towards
+    `budget`."""
     from . import envelope as Env
+    if f0_estimator not in ("dio", "pyin"):
+        raise ValueError(f"f0_estimator must be 'dio' or 'pyin', got {f0_estimator!r}")
     if prosody and not f0:
         raise ValueError("prosody scores need F0: prosody=True cannot go with f0=False")
     if prosody and stft is None:
@@ -522,19 +529,26 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
     def side(wavs, frames):
         staging.pack(wavs)
         y, lens = staging.to(dev), [len(w) for w in wavs]
-        track = None
-        if f0 or world:
+        track = scored = None
+        if world or (f0 and f0_estimator == "dio"):
             from . import pitch as Pitch
             f, _, f_frames = Pitch.dio(y, lens, sampling_rate, frame_period)
-            track = Pitch.stonemask(y, lens, f, f_frames, sampling_rate, frame_period)
+            track = scored = Pitch.stonemask(y, lens, f, f_frames, sampling_rate, frame_period)
+        if f0 and f0_estimator == "pyin":                                   # the scores' track; CheapTrick keeps `track`
+            from . import pyin as Pyin
+            scored = Pyin.pyin(y, lens, sampling_rate, frame_period)[0]
         mel = energy = None
         if prosody or not world:
             mel, energy, _ = stft.mel_spectrogram_ragged(y.clamp(-1.0, 1.0), lens)
         if world:
-            return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), track if f0 else None, energy
-        return cepstra_fn(mel, frames, n_mcep), track, energy
+            return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), scored if f0 else None, energy
+        return cepstra_fn(mel, frames, n_mcep), scored, energy
 
     cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody)     # noqa: E731
+    if f0 and f0_estimator == "pyin":                                       # one side's pYIN chunk workspace lives at a time
+        from . import pyin as Pyin
+        cepstral = cost
+        cost = lambda n, T1, T2: cepstral(n, T1, T2) + Pyin.workspace_bytes(n, max(T1, T2))     # noqa: E731
     for batch in ragged.greedy_batches(list(zip(fr, fs)), budget, cost):
         al, bl = [fr[i] for i in batch], [fs[i] for i in batch]
         a, f0a, ea = side([ref_wavs[i] for i in batch], al)
@@ -559,6 +573,8 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
                 rows[i].update(prosody_scores(q[:8], host[r, 1], q[8:13], q[13:18], q[18], q[19]))
             if world:
                 rows[i].update(cepstra="world", alpha=alpha, fft_size=fft_size)
+            if f0 and f0_estimator != "dio":
+                rows[i]["f0_estimator"] = f0_estimator
     return rows
 
 
@@ -617,17 +633,19 @@ class _Rates:
 
 
 def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=None, score_fn=None,
-        device="cuda", cepstra="mel", alpha=None, prosody=False):
+        device="cuda", cepstra="mel", alpha=None, prosody=False, f0_estimator="dio"):
     """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
     replaces the device stage (called with `prosody=True` as a keyword when that is asked for).  Returns (rows, skipped, summary).
     With cepstra="world" the rows and the summary also say cepstra, alpha and fft_size; with "mel" they are what they were before
     that choice existed.  `prosody` adds the prosody keys of the module docstring and is refused with f0=False before a file is
-    read."""
+    read.  `f0_estimator` "pyin" (score.py --f0 pyin) scores F0 and prosody on pYIN tracks: rows and summary then say f0_estimator."""
     import json
     pp = config["preprocessing"]
     sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
     if prosody and not f0:
         raise ValueError("--prosody needs F0 and cannot go with --no_f0")
+    if f0_estimator not in ("dio", "pyin"):
+        raise ValueError(f"f0_estimator must be 'dio' or 'pyin', got {f0_estimator!r}")
     world_keys = {}
     if cepstra == "world":                                                  # refused before a file is read
         from . import envelope as Env
@@ -641,7 +659,7 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
         stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], pp["mel"]["n_mel_channels"], sr,
                                   pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
         score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device, cepstra=cepstra,     # noqa: E731
-                                            alpha=alpha, prosody=prosody)
+                                            alpha=alpha, prosody=prosody, f0_estimator=f0_estimator)
     elif prosody:
         given = score_fn
         score_fn = lambda r, s: given(r, s, prosody=True)                    # noqa: E731
@@ -654,6 +672,8 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
                 f.write(json.dumps(row) + "\n")
     summary = summarize(rows)
     summary.update(world_keys)
+    if f0 and f0_estimator != "dio":
+        summary["f0_estimator"] = f0_estimator
     summary["skipped"] = len(skipped)
     summary["reference_window"] = {k: sum(1 for r in rows if r["reference_window"] == k) for k in ("textgrid", "whole")}
     return rows, skipped, summary

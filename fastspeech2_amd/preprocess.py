@@ -206,13 +206,13 @@ def _pyworld_pitch():
 
 
 def resolve_pitch(choice):
-    """preprocess.py --pitch: "pyworld" -> None (the host pyworld path), "gpu" -> "gpu", "auto" -> pyworld when importable,
-    else "gpu".  The result is Preprocessor's `pitch` keyword."""
-    if choice not in ("auto", "pyworld", "gpu"):
-        raise ValueError(f"--pitch must be auto, pyworld or gpu, got {choice!r}")
+    """preprocess.py --pitch: "pyworld" -> None (the host pyworld path), "gpu" -> "gpu", "pyin" -> "pyin", "auto" -> pyworld when
+    importable, else "gpu".  The result is Preprocessor's `pitch` keyword."""
+    if choice not in ("auto", "pyworld", "gpu", "pyin"):
+        raise ValueError(f"--pitch must be auto, pyworld, gpu or pyin, got {choice!r}")
     if choice == "auto":
         return None if _pyworld_pitch() is not None else "gpu"
-    return None if choice == "pyworld" else "gpu"
+    return None if choice == "pyworld" else choice
 
 
 # ------------------------------------------------------------------------------------------------ the preprocessor
@@ -221,20 +221,21 @@ class Preprocessor:
                  resample=None):
         """`config` = preprocess.yaml (preprocessor.py:16-51).  `pitch_fn(wav float32, sampling_rate, hop_length) -> f0 per
         frame (0 = unvoiced)` replaces pyworld when that package is absent; `pitch="gpu"` computes F0 on the GPU per ragged
-        batch instead (fastspeech2_amd.pitch); `seed` fixes the train/val shuffle (the reference uses the unseeded global
-        `random`); `resample="gpu"` converts files at another rate than the config's on the GPU, per ragged batch, instead of
-        per file in `load_wav` (needs `pitch="gpu"`: a host pitch backend would need the audio back on the host)."""
+        batch instead (fastspeech2_amd.pitch), `pitch="pyin"` does the same with probabilistic YIN (fastspeech2_amd.pyin);
+        `seed` fixes the train/val shuffle (the reference uses the unseeded global `random`); `resample="gpu"` converts files at another rate than the config's on the GPU, per ragged batch, instead of
+        per file in `load_wav` (needs `pitch="gpu"` or "pyin": a host pitch backend would need the audio back on the host)."""
         if resample not in (None, "gpu"):
             raise ValueError(f"resample must be None or 'gpu', got {resample!r}")
-        if resample == "gpu" and pitch != "gpu":
-            raise ValueError("resample='gpu' needs pitch='gpu': with a host pitch backend the resampled audio would have to come "
-                             "back to the host")
-        if pitch not in (None, "gpu"):
-            raise ValueError(f"pitch must be None or 'gpu', got {pitch!r}")
-        if pitch == "gpu" and pitch_fn is not None:
-            raise ValueError("pass either pitch_fn or pitch='gpu', not both")
-        if pitch == "gpu":
-            ragged.require_device(torch.device(device), "Preprocessor(pitch='gpu'): DIO + StoneMask")
+        if resample == "gpu" and pitch not in ("gpu", "pyin"):
+            raise ValueError("resample='gpu' needs pitch='gpu' or 'pyin': with a host pitch backend the resampled audio would have to "
+                             "come back to the host")
+        if pitch not in (None, "gpu", "pyin"):
+            raise ValueError(f"pitch must be None, 'gpu' or 'pyin', got {pitch!r}")
+        if pitch is not None and pitch_fn is not None:
+            raise ValueError(f"pass either pitch_fn or pitch={pitch!r}, not both")
+        if pitch is not None:
+            ragged.require_device(torch.device(device),
+                                  f"Preprocessor(pitch={pitch!r}): " + ("DIO + StoneMask" if pitch == "gpu" else "pYIN"))
         self.config = config
         self.in_dir = config["path"]["raw_path"]
         self.out_dir = config["path"]["preprocessed_path"]
@@ -308,8 +309,8 @@ class Preprocessor:
             wav = wav[int(self.sampling_rate * start):int(self.sampling_rate * end)].astype(np.float32)
         with open(os.path.join(self.in_dir, speaker, "{}.lab".format(basename)), "r") as f:
             raw_text = f.readline().strip("\n")
-        pitch = None                                                        # pitch="gpu": set by the device stage
-        if self.pitch != "gpu":
+        pitch = None                                                        # pitch="gpu" / "pyin": set by the device stage
+        if self.pitch is None:
             pitch = np.asarray(self.pitch_fn(wav, self.sampling_rate, self.hop_length), dtype=np.float64)[:sum(duration)]
             if np.sum(pitch != 0) <= 1:
                 return None
@@ -332,22 +333,33 @@ class Preprocessor:
         (audio/tools.py:8-15 `get_mel_from_wav` per utterance in the reference: clip to [-1, 1], STFT, squeeze)."""
         return self._features(*self.STFT.mel_spectrogram_ragged(*self._stage(wavs, clip=True)))
 
+    def _f0_batch(self, y, lens):
+        """The chosen device estimator on one ragged batch -> (f0 (B, Fmax) float64 numpy, frames (B,) numpy); one D2H copy."""
+        frame_period = self.hop_length / self.sampling_rate * 1000
+        if self.pitch == "pyin":
+            from . import pyin as Pyin
+            f0, _, _, frames = Pyin.pyin_numpy(y, lens, self.sampling_rate, frame_period)
+        else:
+            from . import pitch as Pitch
+            f0, _, frames = Pitch.dio_stonemask(y, lens, self.sampling_rate, frame_period)
+        return f0, frames
+
     def _extract_pitch(self, wavs):
         """pitch="gpu": [float32 1-D] -> [f0 per DIO frame, float64], DIO + StoneMask on the GPU over the UNCLIPPED audio (the
-        reference's pitch_fn sees the wav before get_mel_from_wav clips it); one H2D and one D2H copy."""
-        from . import pitch as Pitch
-        f0, _, frames = Pitch.dio_stonemask(*self._stage(wavs), self.sampling_rate, self.hop_length / self.sampling_rate * 1000)
+        reference's pitch_fn sees the wav before get_mel_from_wav clips it); one H2D and one D2H copy.  pitch="pyin": the same
+        with pYIN, on the same frame grid."""
+        f0, frames = self._f0_batch(*self._stage(wavs))
         return [f0[b, :f] for b, f in enumerate(frames.tolist())]
 
     def _extract_resampled(self, its):
         """resample="gpu": host-stage items of ONE source rate -> ([f0 per DIO frame], [(mel, energy)]).  One H2D copy of the input
         spans, `resample_poly` of each row's trim window, then F0 on its unclipped and the STFT on its clamped output."""
-        from . import pitch as Pitch, resample as R
+        from . import resample as R
         x, lens = self._stage([it["wav"] for it in its])
         y, yc, out_lens = R.resample_poly(x, lens, its[0]["sr"], self.sampling_rate,
                                           out_begin=[it["out_begin"] for it in its], out_len=[it["out_len"] for it in its],
                                           clip=True, in_begin=[it["in_begin"] for it in its])
-        f0, _, f0_frames = Pitch.dio_stonemask(y, out_lens, self.sampling_rate, self.hop_length / self.sampling_rate * 1000)
+        f0, f0_frames = self._f0_batch(y, out_lens)
         return ([f0[b, :f] for b, f in enumerate(f0_frames.tolist())],
                 self._features(*self.STFT.mel_spectrogram_ragged(yc, out_lens)))
 
@@ -387,9 +399,9 @@ class Preprocessor:
 
     # ---------------------------------------------------------------- the corpus pass
     def build_from_path(self):
-        if self.pitch_fn is None and self.pitch != "gpu":
+        if self.pitch_fn is None and self.pitch is None:
             self.pitch_fn = _pyworld_pitch()
-        if self.pitch_fn is None and self.pitch != "gpu":
+        if self.pitch_fn is None and self.pitch is None:
             raise RuntimeError("pyworld is not installed: pass pitch_fn=(wav, sampling_rate, hop_length) -> f0 per frame, "
                                "or pitch=\"gpu\" for DIO + StoneMask on the GPU")
         for d in ("mel", "pitch", "energy", "duration"):
@@ -421,7 +433,7 @@ class Preprocessor:
                     pitches, mels = self._extract_resampled([items[i] for i in batch])
                 else:
                     wavs = [items[i]["wav"] for i in batch]
-                    pitches = self._extract_pitch(wavs) if self.pitch == "gpu" else None
+                    pitches = self._extract_pitch(wavs) if self.pitch is not None else None
                     mels = self._extract_mels(wavs)
                 for j, (i, (mel, energy)) in enumerate(zip(batch, mels)):
                     items[i]["wav"] = None                                  # release the audio once its features exist

@@ -393,6 +393,26 @@ int fs2_f0_fix(const double* cand, const double* score, const int32_t* frames, i
 int fs2_f0_stonemask(const float* x, long ldx, const int32_t* lens, const double* f0, const int32_t* frames, double fs,
                      double frame_period, double* out, int B, int Fmax, int Nmax, fs2_stream_t stream);
 
+/* ---- F0: probabilistic YIN (Mauch & Dixon 2014; specification: fastspeech2_amd/pyin.py) ----
+ * fp64 throughout, the same ragged float32 rows as above; three stages, each taking the previous one's output, fixed-order sums,
+ * no atomics.  Frame f of row b is centred at sample f hop and spans frame_length samples (zero outside [0, lens[b])); every output
+ * row at f >= frames[b] is written as 0.
+ * fs2_pyin_cmnd: cumulative-mean-normalised difference d'[B][Fmax][tmax + 1], integration window frame_length / 2, direct form
+ * (tmax <= frame_length / 2 - 1). */
+int fs2_pyin_cmnd(const float* x, long ldx, const int32_t* lens, const int32_t* frames, int hop, int frame_length, int tmax,
+                  double* dprime, int B, int Fmax, int Nmax, fs2_stream_t stream);
+/* troughs of d' on [tmin, tmax], the nthr threshold weights beta[k] (threshold (k + 1) / nthr) -> obs[B][Fmax][2 nb]: nb voiced pitch
+ * bins (bin = round(bins_per_octave log2(f / fmin))), then nb equal unvoiced entries (1 - pv) / nb; pv[B][Fmax] = min(sum, 1) */
+int fs2_pyin_observe(const double* dprime, const int32_t* frames, int tmin, int tmax, const double* beta, int nthr,
+                     double no_trough_prob, double fs, double fmin, int bins_per_octave, int nb, double* obs, double* pv,
+                     int B, int Fmax, fs2_stream_t stream);
+/* Viterbi over the 2 nb states (state = v nb + bin, v = 0 voiced): logw[2 half_width + 1] the band's log weights, logz[nb] the log of
+ * each source bin's in-range weight sum; backptr [B][Fmax][2 nb] bytes of workspace ((offset, flip) in one byte: 2 (2 half_width + 1)
+ * above 255 is FS2_EINVAL) -> states[B][Fmax], f0[B][Fmax] = fmin 2^(bin / bins_per_octave) or 0 */
+int fs2_pyin_viterbi(const double* obs, const int32_t* frames, int nb, int half_width, const double* logw, const double* logz,
+                     double switch_prob, double fmin, int bins_per_octave, uint8_t* backptr, int32_t* states, double* f0,
+                     int B, int Fmax, fs2_stream_t stream);
+
 /* ---- forced alignment: monophone HMM, Baum-Welch + Viterbi (specification: fastspeech2_amd/align.py) ----
  * fp64 throughout, ragged batches: utterance b has lens[b] frames and jlens[b] states (both int32, device); buffers are
  * [B][Tmax][Jmax] with explicit batch / frame strides in elements, graph rows sid / skip / block are [B][Jmax] int32 with row stride

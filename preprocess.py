@@ -13,8 +13,9 @@ if __name__ == "__main__":
     parser.add_argument("--batch_seconds", type=float, default=1800.0, help="audio per ragged STFT batch on the GPU")
     parser.add_argument("--num_workers", type=int, default=8, help="host threads for TextGrid / wav / F0")
     parser.add_argument("--seed", type=int, default=None, help="seed of the train/val shuffle (reference: unseeded)")
-    parser.add_argument("--pitch", choices=["auto", "pyworld", "gpu"], default="auto",
-                        help="F0: pyworld on the host, or DIO + StoneMask on the GPU; auto = pyworld when importable, else gpu")
+    parser.add_argument("--pitch", choices=["auto", "pyworld", "gpu", "pyin"], default="auto",
+                        help="F0: pyworld on the host, DIO + StoneMask on the GPU (gpu) or probabilistic YIN on the GPU (pyin); "
+                             "auto = pyworld when importable, else gpu")
     parser.add_argument("--resample", choices=["host", "gpu"], default="host",
                         help="files at another rate than the config's: polyphase resampling per file on the host, or per ragged "
                              "batch on the GPU (needs the GPU pitch backend)")

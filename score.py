@@ -2,7 +2,7 @@
 """score.py — objective scores of synthesized against recorded speech on the GPU (fastspeech2_amd/metrics.py):
 
     python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
-                    [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--out scores.jsonl]
+                    [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--f0 {dio,pyin}] [--out scores.jsonl]
 
 For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
 is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
@@ -16,7 +16,9 @@ rows and summary also carry `cepstra`, `alpha` and `fft_size`.  Agreement with t
 With `--prosody` (not with `--no_f0`) every row and the summary also carry the numbers FastSpeech 2 evaluates its variance adaptor by:
 gross pitch error, F0 frame error and log-F0 correlation on the path, the DTW distance between the voiced pitch contours in Hz, the
 mean absolute error of the frame energy, and the standard deviation, skewness and excess kurtosis of the voiced F0 of both sides.
-The paper does not say how it treats unvoiced frames or in which unit its DTW distance is: these compare runs of this tool."""
+The paper does not say how it treats unvoiced frames or in which unit its DTW distance is: these compare runs of this tool.
+With `--f0 pyin` both sides of every F0 and prosody number come from probabilistic YIN (fastspeech2_amd/pyin.py) instead of DIO +
+StoneMask, an independent estimator to cross-check the pitch scores with; rows and summary then carry `f0_estimator`."""
 import argparse
 import json
 import sys
@@ -41,6 +43,9 @@ def parse_args(argv=None):
     parser.add_argument("--n_mcep", type=int, default=None, help="cepstral coefficients 1..n_mcep (at most 40; default 13 mel, 24 world)")
     parser.add_argument("--prosody", action="store_true",
                         help="also GPE, FFE, log-F0 correlation, pitch-contour DTW, energy MAE and the pitch moments (needs F0)")
+    parser.add_argument("--f0", choices=("dio", "pyin"), default="dio",
+                        help="estimator of both sides of every F0 and prosody score: DIO + StoneMask or probabilistic YIN; with --cepstra "
+                             "world CheapTrick keeps its own DIO + StoneMask F0 whatever this says")
     parser.add_argument("--out", type=str, default="scores.jsonl")
     parser.add_argument("--device", type=str, default="cuda")
     return parser.parse_args(argv)
@@ -54,7 +59,7 @@ def main(argv=None, score_fn=None):
         rows, skipped, summary = metrics.run(config, train["path"]["result_path"], args.source, out_path=args.out, syn_dir=args.syn_dir,
                                              ref_dir=args.ref_dir, trim=not args.no_trim, f0=not args.no_f0, n_mcep=args.n_mcep,
                                              score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha,
-                                             prosody=args.prosody)
+                                             prosody=args.prosody, f0_estimator=args.f0)
     except ValueError as e:
         sys.exit(str(e))
     for name, reason in skipped:
