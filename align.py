@@ -13,6 +13,8 @@ if __name__ == "__main__":
     parser.add_argument("config", type=str, help="path to preprocess.yaml")
     parser.add_argument("--states", type=int, default=2, help="HMM states per phone (1..3)")
     parser.add_argument("--iters", type=int, default=12, help="Baum-Welch passes after the flat start")
+    parser.add_argument("--mixtures", type=int, default=1, help="Gaussian mixture components per state, grown by splitting (1..8)")
+    parser.add_argument("--mix_iters", type=int, default=4, help="Baum-Welch passes after every split")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -22,7 +24,8 @@ if __name__ == "__main__":
     config = yaml.load(open(args.config, "r"), Loader=yaml.FullLoader)
     try:
         written, skipped, history = build(config, device=args.device, states=args.states, iters=args.iters, overwrite=args.overwrite,
-                                          batch_bytes=int(args.batch_gib * (1 << 30)), num_workers=args.num_workers)
+                                          batch_bytes=int(args.batch_gib * (1 << 30)), num_workers=args.num_workers, mixtures=args.mixtures,
+                                          mix_iters=args.mix_iters)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))

@@ -41,6 +41,30 @@ Decoding.  Viterbi with the same arcs: delta[t, j] = E[t, j] + max over (self, n
 ties; among the end states the lower index wins ties.  Backtracking gives frames per block; a skipped optional block has 0 frames
 and is not written.  Block boundaries are at f hop / sampling_rate seconds, f the cumulative frame count; the last one is xmax.
 
+Mixtures (`mixtures` = M > 1; the default M = 1 is everything above, unchanged).  Every HMM recipe (HTK, Kaldi, MFA) grows its
+flat-start monophones into Gaussian mixtures by splitting; a single Gaussian cannot hold a phone that is realised in more than one
+way (speakers, allophones, stress), its variance inflates until neighbouring phones overlap.
+  Model.  Class c has K_c active components, 1 <= K_c <= M, M in 1..`max_mixtures()` (8).  Tables w (C, M), mu (C, M, D), var (C, M, D),
+  float64.  Components m >= K_c are inactive: w = 0, mu = 0, var = 1, never updated.
+  Emission.  For component m of the class of state j:  N[t, j, m] = log w_m - 1/2 sum_d ((x_d - mu_d)^2 / var_d + log(2 pi var_d)), the
+  sum over d of the form and order above, log 0 = -inf.  E[t, j] = mx + log(sum_m exp(N_m - mx)), mx = max_m N_m, the sum over
+  ascending m (-inf when mx is).  Responsibilities r[t, j, m] = exp(N_m - E[t, j]); a component with w = 0 gets exactly 0.  With M = 1
+  and w = 1 this is the E above bit for bit (log 1 = 0, exp 0 = 1, mx + log 1 = mx).
+  Statistics.  Per utterance partials [J][M][1 + 2 D]: the sum over ascending t of gamma[t, j] r[t, j, m] [1, x, x^2].  The class sums are
+  the reduction above with component m of class c as row class c M + m and the partial row of (utterance b, state j, component m)
+  as row (b ld_j + j) M + m, listed utterances first, then states ascending.
+  Update (host, numpy).  n_c = sum over the active m of n_cm, ascending.  n_c >= 1: w_cm = n_cm / n_c; else the weights are kept.  An
+  active component with n_cm >= 1 gets mu = a / n, var = max(q / n - mu^2, floor); one with n_cm < 1 keeps mu and var.  The floor is
+  the one above.
+  Schedule.  The flat start and the `iters` passes with one component, exactly as above; then for k = 1 .. M - 1: split, then
+  `mix_iters` passes (default 4, a choice).
+  Split of class c at step k.  h = the active component of the largest weight, the lowest index on ties.  If K_c < k + 1 and the
+  occupancy n_ch of h in the last pass is at least `min_split_occ` (default 40 frames, a choice), component K_c becomes active: both
+  halves get the weight w_h / 2, mu_new = mu_h + 0.2 sqrt(var_h), mu_h becomes mu_h - 0.2 sqrt(var_h), the variance is copied.  A
+  class that fails the condition keeps its components (a rare `sp` or `spn` may never split).
+  `fit` returns the log-likelihood per frame of every pass of every stage, in order, and logs K_c per stage.  Decoding takes E from
+  the mixture emission (no responsibilities); Viterbi and backtracking are unchanged.  Nothing of this has been measured against MFA.
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
 update runs on the host in numpy.  Two runs over one corpus write byte-identical TextGrids.
@@ -128,6 +152,40 @@ def m_step(sums, mu, var, floor):
     return np.where(ok[:, None], m, mu), np.where(ok[:, None], v, var)
 
 
+def m_step_gmm(sums, w, mu, var, ncomp, floor):
+    """The mixture update of the module docstring on class sums (C, M, 1 + 2 D) -> (w, mu, var); inactive components are left alone."""
+    C, M, D = mu.shape
+    sums = np.asarray(sums).reshape(C, M, 1 + 2 * D)
+    active = np.arange(M)[None, :] < np.asarray(ncomp)[:, None]
+    n = np.where(active, sums[:, :, 0], 0.0)
+    n_c = np.zeros(C)
+    for m in range(M):                                                     # ascending m, as specified
+        n_c = n_c + n[:, m]
+    keep_w = n_c < 1.0
+    w_new = np.where(keep_w[:, None] | ~active, w, n / np.where(keep_w, 1.0, n_c)[:, None])
+    ok = active & (n >= 1.0)
+    nn = np.where(ok, n, 1.0)[:, :, None]
+    m_new = sums[:, :, 1:1 + D] / nn
+    v_new = np.maximum(sums[:, :, 1 + D:] / nn - m_new * m_new, floor[None, None, :])
+    return w_new, np.where(ok[:, :, None], m_new, mu), np.where(ok[:, :, None], v_new, var)
+
+
+def split_classes(w, mu, var, ncomp, occ, k, min_split_occ=40.0, step=0.2):
+    """Split step k of the module docstring: occ (C, M) is the occupancy of every component in the last pass -> (w, mu, var, ncomp)."""
+    w, mu, var, ncomp = w.copy(), mu.copy(), var.copy(), np.array(ncomp, dtype=np.int64)
+    occ = np.asarray(occ).reshape(w.shape)
+    for c in range(w.shape[0]):
+        K = int(ncomp[c])
+        h = int(np.argmax(w[c, :K]))                                       # the first of the largest
+        if K < k + 1 and K < w.shape[1] and occ[c, h] >= min_split_occ:
+            d = step * np.sqrt(var[c, h])
+            w[c, h] = w[c, K] = w[c, h] / 2.0
+            mu[c, K], mu[c, h] = mu[c, h] + d, mu[c, h] - d
+            var[c, K] = var[c, h]
+            ncomp[c] = K + 1
+    return w, mu, var, ncomp
+
+
 # ------------------------------------------------------------------------------------------------ TextGrid
 def write_textgrid(path, words, phones, xmax):
     """Long Praat text format, IntervalTiers `words` and `phones` of (start, end, text) intervals; times are written with repr, so
@@ -168,6 +226,10 @@ def max_states():
     return _lib.load().fs2_align_max_states()
 
 
+def max_mixtures():
+    return _lib.load().fs2_align_max_mixtures()
+
+
 def _dev(t, dtype, what, dim=3):
     ragged.require_device(t, "fastspeech2_amd.align")
     if t.dtype != dtype or t.dim() != dim or (t.numel() and t.stride(-1) != 1):
@@ -195,13 +257,18 @@ class Graphs:
         self.jlens = torch.tensor(self.jl, dtype=torch.int32, device=device)
         self.ldg = max(self.Jmax, 1)
 
-    def index(self, n_classes, ld_j):
-        """CSR (class -> rows b * ld_j + j of the partials), utterances then states ascending: (offs, items) on the device."""
+    def index(self, n_classes, ld_j, mixtures=1):
+        """CSR (class -> rows b * ld_j + j of the partials), utterances then states ascending: (offs, items) on the device.  With
+        `mixtures` = M > 1 the row classes are c * M + m and the rows (b * ld_j + j) * M + m, in the same order within a row class."""
         cls = np.concatenate([g["sid"].astype(np.int64) for g in self.graphs]) if self.graphs else np.zeros(0, np.int64)
         rows = np.concatenate([b * ld_j + np.arange(n, dtype=np.int64) for b, n in enumerate(self.jl)]) if self.graphs \
             else np.zeros(0, np.int64)
         if cls.size and (cls.min() < 0 or cls.max() >= n_classes):
             raise ValueError(f"emission class outside [0, {n_classes})")
+        if mixtures > 1:
+            comp = np.arange(mixtures, dtype=np.int64)[None, :]
+            cls, rows = (cls[:, None] * mixtures + comp).ravel(), (rows[:, None] * mixtures + comp).ravel()
+            n_classes *= mixtures
         order = np.argsort(cls, kind="stable")
         offs = np.zeros(n_classes + 1, np.int64)
         np.cumsum(np.bincount(cls, minlength=n_classes), out=offs[1:])
@@ -247,6 +314,48 @@ def emit(x, lens, G, mu, var, out=None):
     return E
 
 
+def _no_host(**tensors):
+    for what, t in tensors.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device.type != "cuda"):
+            raise ValueError(f"{what} must be a tensor on the GPU (fastspeech2_amd.align has no CPU fallback)")
+
+
+def _check_mix(w, mu, var, D):
+    w = _dev(w, torch.float64, "w", 2).contiguous()
+    mu, var = _dev(mu, torch.float64, "mu", 3).contiguous(), _dev(var, torch.float64, "var", 3).contiguous()
+    M = w.shape[1]
+    if not 1 <= M <= max_mixtures():
+        raise ValueError(f"{M} mixture components, supported are 1..{max_mixtures()}")
+    if mu.shape != var.shape or mu.shape[:2] != w.shape or mu.shape[2] != D or w.shape[0] == 0:
+        raise ValueError(f"w {tuple(w.shape)}, mu {tuple(mu.shape)}, var {tuple(var.shape)} and D = {D} do not fit together")
+    return w, mu, var, M
+
+
+def emit_gmm(x, lens, G, w, mu, var, out=None, resp=None):
+    """E (B, Tmax, Jmax) float64 from the mixture tables w (C, M), mu, var (C, M, D); responsibilities are written to `resp`
+    (B, >= Tmax, >= Jmax, M) when it is given (decoding passes none)."""
+    _no_host(x=x, w=w, mu=mu, var=var, out=out, resp=resp)
+    x = _dev(x, torch.float64, "x")
+    B, Tmax, D = x.shape
+    w, mu, var, M = _check_mix(w, mu, var, D)
+    if B != len(G.jl):
+        raise ValueError(f"x {tuple(x.shape)} and {len(G.jl)} graphs do not fit together")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", x.device)
+    E = torch.empty(B, Tmax, G.Jmax, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
+    if E.shape[0] != B or E.shape[1] < Tmax or E.shape[2] < G.Jmax:
+        raise ValueError(f"out {tuple(E.shape)} is too small for ({B}, {Tmax}, {G.Jmax})")
+    rp, rs = None, (0, 0, 0)
+    if resp is not None:
+        resp = _dev(resp, torch.float64, "resp", 4)
+        if resp.shape[0] != B or resp.shape[1] < Tmax or resp.shape[2] < G.Jmax or resp.shape[3] != M:
+            raise ValueError(f"resp {tuple(resp.shape)} is not ({B}, >= {Tmax}, >= {G.Jmax}, {M})")
+        rp, rs = resp.data_ptr(), resp.stride()[:3]
+    _lib.call("fs2_align_emit_gmm", x.data_ptr(), x.stride(0), x.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.sid.data_ptr(),
+              G.ldg, w.data_ptr(), mu.data_ptr(), var.data_ptr(), w.shape[0], M, D, E.data_ptr(), E.stride(0), E.stride(1), rp, rs[0],
+              rs[1], rs[2], B, Tmax, G.Jmax, ops._stream())
+    return E
+
+
 def forward(E, lens, G, out=None):
     """-> (alpha like E, loglik (B,)) on the device."""
     E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
@@ -289,8 +398,37 @@ def stats(gamma, x, lens, G, out=None):
     return P
 
 
+def stats_gmm(gamma, resp, x, lens, G, out=None):
+    """Per-utterance mixture partials (B, Jmax, M, 1 + 2 D) of gamma (B, T, J) and the responsibilities resp (B, T, J, M)."""
+    _no_host(gamma=gamma, resp=resp, x=x, out=out)
+    gamma, B, Tmax, _, lens_d = _check_scan(gamma, lens, G)
+    x, resp = _dev(x, torch.float64, "x"), _dev(resp, torch.float64, "resp", 4)
+    D, M = x.shape[2], resp.shape[3]
+    if not 1 <= M <= max_mixtures():
+        raise ValueError(f"{M} mixture components, supported are 1..{max_mixtures()}")
+    if x.shape[0] != B or x.shape[1] < Tmax:
+        raise ValueError(f"x {tuple(x.shape)} does not cover gamma {tuple(gamma.shape)}")
+    if resp.shape[0] != B or resp.shape[1] < Tmax or resp.shape[2] < G.Jmax:
+        raise ValueError(f"resp {tuple(resp.shape)} does not cover gamma {tuple(gamma.shape)}")
+    P = torch.empty(B, G.ldg, M, 1 + 2 * D, dtype=torch.float64, device=x.device) if out is None \
+        else _dev(out, torch.float64, "out", 4)
+    if P.shape[0] != B or P.shape[1] < G.Jmax or P.shape[2] != M or P.shape[3] != 1 + 2 * D or P.stride(1) != M * P.stride(2):
+        raise ValueError(f"out {tuple(P.shape)} is not ({B}, >= {G.Jmax}, {M}, {1 + 2 * D}) with the components of a state together")
+    _lib.call("fs2_align_stats_gmm", gamma.data_ptr(), gamma.stride(0), gamma.stride(1), resp.data_ptr(), resp.stride(0),
+              resp.stride(1), resp.stride(2), x.data_ptr(), x.stride(0), x.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), M, D,
+              P.data_ptr(), P.stride(0), P.stride(2), B, Tmax, G.Jmax, ops._stream())
+    return P
+
+
 def reduce(P, G, n_classes, sums=None, index=None):
-    """Class sums (C, 1 + 2 D) of the partials; added to `sums` when given."""
+    """Class sums (C, 1 + 2 D) of the partials; added to `sums` when given.  Mixture partials (B, J, M, 1 + 2 D) give (C M, 1 + 2 D),
+    component m of class c in row c M + m."""
+    if P.dim() == 4:
+        if not P.is_contiguous():
+            raise ValueError("partials must be contiguous")
+        M = P.shape[2]
+        index = index if index is not None else G.index(n_classes, P.shape[1], M)
+        return reduce(P.view(P.shape[0], P.shape[1] * M, P.shape[3]), G, n_classes * M, sums, index)
     P = _dev(P, torch.float64, "partials")
     if not P.is_contiguous():
         raise ValueError("partials must be contiguous")
@@ -334,9 +472,11 @@ def backtrack(bp, lens, G, end):
 
 # ------------------------------------------------------------------------------------------------ the model
 class Aligner:
-    """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`."""
+    """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`.  With `mixtures` = M > 1
+    `fit` goes on from that table to the mixture tables gw (n_classes, M), gmu, gvar (n_classes, M, dim) on the device and ncomp
+    (active components per class, numpy), and `align` decodes with those."""
 
-    def __init__(self, n_classes, dim, states=2, device="cuda"):
+    def __init__(self, n_classes, dim, states=2, device="cuda", mixtures=1, mix_iters=4, min_split_occ=40):
         self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
         if n_classes % states:
             raise ValueError(f"n_classes {n_classes} is not a multiple of states {states}")
@@ -344,6 +484,17 @@ class Aligner:
         self.mu = torch.zeros(n_classes, dim, dtype=torch.float64, device=self.device)
         self.var = torch.ones(n_classes, dim, dtype=torch.float64, device=self.device)
         self.floor = np.zeros(dim)
+        self.mixtures, self.mix_iters, self.min_split_occ = int(mixtures), int(mix_iters), float(min_split_occ)
+        if self.mixtures != 1:
+            if not 1 <= self.mixtures <= max_mixtures():
+                raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
+            if self.mix_iters < 1:
+                raise ValueError(f"mix_iters must be at least 1, got {mix_iters}")
+            self.gw = torch.zeros(n_classes, self.mixtures, dtype=torch.float64, device=self.device)
+            self.gw[:, 0] = 1.0
+            self.gmu = torch.zeros(n_classes, self.mixtures, dim, dtype=torch.float64, device=self.device)
+            self.gvar = torch.ones(n_classes, self.mixtures, dim, dtype=torch.float64, device=self.device)
+            self.ncomp = np.ones(n_classes, np.int64)
 
     def _prepare(self, feats, lens, graphs):
         lens = [int(v) for v in lens]
@@ -364,7 +515,7 @@ class Aligner:
 
     def fit(self, batches, iters=12):
         """batches: [(feats (B, Tmax, D) float64 on the device or the host, lens, graphs)].  Flat start, then `iters` Baum-Welch
-        passes; returns the log-likelihood per frame of every pass."""
+        passes (then, with mixtures, the split stages); returns the log-likelihood per frame of every pass."""
         prep = []
         for feats, lens, graphs in batches:
             lens, G = self._prepare(feats, lens, graphs)
@@ -405,36 +556,79 @@ class Aligner:
                 sums = reduce(stats(gamma, x, lens, G), G, self.n_classes, sums, index)
                 total += float(np.sum(loglik.cpu().numpy()))
                 del E, alpha, gamma
-            mu, var = m_step(sums.cpu().numpy(), mu, var, self.floor)
+            s = sums.cpu().numpy()
+            mu, var = m_step(s, mu, var, self.floor)
             self._set(mu, var)
             history.append(total / n_frames)
+        if self.mixtures > 1:
+            history += self._fit_mixtures(prep, n_frames, s[:, 0], mu, var)
+        return history
+
+    def _fit_mixtures(self, prep, n_frames, occ0, mu, var):
+        """The split stages k = 1 .. M - 1 from the one-component table (mu, var) whose last pass had the occupancies occ0."""
+        C, M, D = self.n_classes, self.mixtures, self.dim
+        w, gmu, gvar = np.zeros((C, M)), np.zeros((C, M, D)), np.ones((C, M, D))
+        w[:, 0], gmu[:, 0], gvar[:, 0] = 1.0, mu, var
+        ncomp, occ = np.ones(C, np.int64), np.zeros((C, M))
+        occ[:, 0] = occ0
+        index = [G.index(C, G.ldg, M) for _, _, G, _ in prep]
+        history = []
+        for k in range(1, M):
+            w, gmu, gvar, ncomp = split_classes(w, gmu, gvar, ncomp, occ, k, self.min_split_occ)
+            print(f"mixtures: stage {k + 1}, classes by active components " +
+                  " ".join(f"{n}:{int(np.sum(ncomp == n))}" for n in range(1, M + 1) if np.any(ncomp == n)))
+            for _ in range(self.mix_iters):
+                for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
+                    dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+                sums, total = None, 0.0
+                for (feats, lens, G, _), idx in zip(prep, index):
+                    x = feats.to(self.device, non_blocking=True)
+                    resp = torch.empty(x.shape[0], x.shape[1], G.ldg, M, dtype=torch.float64, device=self.device)
+                    E = emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar, resp=resp)
+                    alpha, loglik = forward(E, lens, G)
+                    gamma = backward(E, lens, G, alpha, loglik)
+                    sums = reduce(stats_gmm(gamma, resp, x, lens, G), G, C, sums, idx)
+                    total += float(np.sum(loglik.cpu().numpy()))
+                    del E, alpha, gamma, resp
+                s = sums.cpu().numpy().reshape(C, M, 1 + 2 * D)
+                occ = s[:, :, 0]
+                w, gmu, gvar = m_step_gmm(s, w, gmu, gvar, ncomp, self.floor)
+                history.append(total / n_frames)
+        for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
+            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+        self.ncomp = ncomp
         return history
 
     def align(self, feats, lens, graphs):
         """Viterbi alignment of one ragged batch -> [frames per block (int32 numpy)] per utterance."""
         lens, G = self._prepare(feats, lens, graphs)
         x = feats.to(self.device, non_blocking=True)
-        E = emit(x, lens, G, self.mu, self.var)
+        E = emit(x, lens, G, self.mu, self.var) if self.mixtures == 1 else emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar)
         bp, end, _ = viterbi(E, lens, G)
         frames = backtrack(bp, lens, G, end).cpu().numpy()
         return [frames[b, :len(g["blocks"])].copy() for b, g in enumerate(graphs)]
 
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
-def batches_by_bytes(frames, states, dim, budget):
+def batches_by_bytes(frames, states, dim, budget, mixtures=1):
     """`ragged.greedy_batches` of (frames, states) under `budget` bytes of device buffers: E, alpha / gamma and backpointers (17 B per
-    cell), features, partials."""
-    cost = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
+    cell), features, partials; with `mixtures` = M > 1 also the responsibilities (8 M B per cell) and M times the partials."""
+    if mixtures == 1:
+        cost = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
+    else:
+        cost = lambda n, T, J: n * (T * J * (17 + 8 * mixtures) + T * dim * 8 + J * mixtures * (1 + 2 * dim) * 8)  # noqa: E731
     return ragged.greedy_batches(list(zip(frames, states)), budget, cost)
 
 
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
-          batch_seconds=1800.0, num_workers=8):
+          batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
     from . import audio as Audio
     from .preprocess import load_wav
     dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
+    if not 1 <= mixtures <= max_mixtures():
+        raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
     raw, out_dir = config["path"]["raw_path"], os.path.join(config["path"]["preprocessed_path"], "TextGrid")
     pp = config["preprocessing"]
     sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
@@ -504,13 +698,13 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     frames, nstates = [it["x"].shape[0] for it in items], [len(it["graph"]["sid"]) for it in items]
     resident = sum(frames) * D * 8 <= resident_bytes
     packed = []
-    for batch in batches_by_bytes(frames, nstates, D, batch_bytes):
+    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures):
         feats = torch.zeros(len(batch), max(frames[i] for i in batch), D, dtype=torch.float64)
         for r, i in enumerate(batch):
             feats[r, :frames[i]] = items[i]["x"]
             items[i]["x"] = None
         packed.append((feats.to(dev) if resident else feats, [frames[i] for i in batch], [items[i]["graph"] for i in batch], batch))
-    aligner = Aligner(len(phone_ids) * states, D, states, dev)
+    aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters)
     history = aligner.fit([p[:3] for p in packed], iters)
 
     written = 0

@@ -10,17 +10,20 @@
 //   fs2_align_feats      log-mel [B][n_mel][frames] f32 -> x [B][Tmax][2 n_mel] f64: per-utterance mean removed, central differences
 //   fs2_align_emit       E[b][t][j] = -1/2 sum_d ((x_d - mu_d)^2 / var_d + log(2 pi var_d)) for class sid[b][j]; 32 x 32 tiles of
 //                        (t, j), the class rows staged in LDS as mu, 1 / var and log(2 pi var)
+//   fs2_align_emit_gmm   the same with up to 8 mixture components per class: E = log sum_m exp(N_m), optional responsibilities
 //   fs2_align_forward    the three scans: one workgroup per utterance, one state per lane, the previous frame's row in LDS,
 //   fs2_align_backward   double-buffered, so a frame costs one barrier; E / alpha / gamma rows are read and written as
 //   fs2_align_viterbi    consecutive f64 (bytes for the backpointers), the next frame's operands are loaded one frame ahead
 //   fs2_align_stats      P[b][j] = sum_t gamma[t][j] [1, x_t, x_t^2]: gamma^T [1 x x^2] per utterance, 32 x 32 tiles of (j, d), frames
 //                        staged in LDS 32 at a time, summed in ascending t
+//   fs2_align_stats_gmm  the same over rows (j, m) with g = gamma[t][j] r[t][j][m], multiplied while a frame block is staged
 //   fs2_align_reduce     class sums from the partial rows a host-built CSR index lists, in list order (no atomics anywhere)
 //   fs2_align_backtrack  backpointers -> frames per block, one lane per utterance
 #include "fs2_common.h"
 
 #define AL_MAX_STATES 1024          // one state per lane of the largest workgroup
 #define AL_TILE 32
+#define AL_MAX_MIX 8                // mixture components per class: a lane keeps its 4 x 8 component scores in registers
 
 static __device__ __forceinline__ int al_len(const int32_t* lens, int b, int cap) { return min(max(lens[b], 0), cap); }
 static __device__ __forceinline__ double al_ninf() { return -__builtin_huge_val(); }
@@ -162,6 +165,131 @@ extern "C" int fs2_align_emit(const double* x, long ldx_b, long ldx_t, const int
     align_emit_kernel<<<dim3(fs2_cdiv(Jmax, AL_TILE), fs2_cdiv(Tmax, AL_TILE), B), 256, 0, stream>>>(
         x, ldx_b, ldx_t, lens, jlens, sid, ldg, mu, var, n_classes, D, E, lde_b, lde_t, Tmax, Jmax);
     FS2_CHECK_LAUNCH("align_emit");
+    return FS2_OK;
+}
+
+// Mixture emissions.  The tile and the lane map of align_emit_kernel; the components are the outer loop, so the D-chunks of x are
+// staged once per component (they come from L2 after the first) and LDS stays at the single-Gaussian kernel's 34 KiB for any D,
+// where a whole 32-frame tile of x would take 40 KiB at D = 160 and grow with D.  Component m of class c is row c * M + m of the
+// tables.  A lane keeps N[m][q] = log w_m - 1/2 sum_d (...) of its four outputs in registers (the loop over m is unrolled), then
+// takes the maximum and the sum over ascending m.  log 0 = -inf: a component of weight 0 has responsibility exp(-inf) = 0.
+template <int M>
+__global__ void __launch_bounds__(256) align_emit_gmm_kernel(const double* __restrict__ x, long ldx_b, long ldx_t,
+                                                             const int32_t* __restrict__ lens, const int32_t* __restrict__ jlens,
+                                                             const int32_t* __restrict__ sid, long ldg, const double* __restrict__ w,
+                                                             const double* __restrict__ mu, const double* __restrict__ var,
+                                                             int n_classes, int D, double* __restrict__ E, long lde_b, long lde_t,
+                                                             double* __restrict__ resp, long ldr_b, long ldr_t, long ldr_j, int Tmax,
+                                                             int Jmax) {
+    __shared__ double xs[AL_TILE][AL_TILE + 1], ms[AL_TILE][AL_TILE + 1], vs[AL_TILE][AL_TILE + 1], ls[AL_TILE][AL_TILE + 1];
+    __shared__ double lw[AL_TILE];
+    __shared__ int cls[AL_TILE];
+    const int b = blockIdx.z, T = al_len(lens, b, Tmax), J = al_len(jlens, b, Jmax);
+    const int t0 = blockIdx.y * AL_TILE, j0 = blockIdx.x * AL_TILE, tid = threadIdx.x;
+    if (t0 >= T || j0 >= J) return;
+    if (tid < AL_TILE) {
+        const int j = j0 + tid;
+        const int c = j < J ? sid[(size_t)b * ldg + j] : -1;
+        cls[tid] = (c >= 0 && c < n_classes) ? c : -1;                     // a class outside the table yields NaN, never a wild read
+    }
+    const int jj = tid & 31, tg = tid >> 5;
+    const double* xb = x + (size_t)b * ldx_b;
+    double N[M][4];
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int d0 = 0; d0 < D; d0 += AL_TILE) {
+            __syncthreads();
+            if (d0 == 0 && tid < AL_TILE) {
+                const int c = cls[tid];
+                lw[tid] = c >= 0 ? log(w[(size_t)c * M + m]) : 0.0;
+            }
+            for (int k = tid; k < AL_TILE * AL_TILE; k += 256) {
+                const int r = k >> 5, dd = k & 31, d = d0 + dd;
+                const int t = t0 + r;
+                xs[r][dd] = (t < T && d < D) ? xb[(size_t)t * ldx_t + d] : 0.0;
+                const int c = cls[r];
+                double mm = 0.0, iv = 0.0, lg = 0.0;
+                if (d < D) {
+                    if (c >= 0) {
+                        const size_t at = ((size_t)c * M + m) * D + d;
+                        const double v = var[at];
+                        mm = mu[at];
+                        iv = 1.0 / v;
+                        lg = log(6.283185307179586476925286766559 * v);
+                    } else if (j0 + r < J) {
+                        lg = __builtin_nan("");
+                    }
+                }
+                ms[r][dd] = mm;
+                vs[r][dd] = iv;
+                ls[r][dd] = lg;
+            }
+            __syncthreads();
+#pragma unroll 4
+            for (int dd = 0; dd < AL_TILE; ++dd) {
+                const double mm = ms[jj][dd], iv = vs[jj][dd], lg = ls[jj][dd];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double df = xs[tg + 8 * q][dd] - mm;
+                    acc[q] += df * df * iv + lg;
+                }
+            }
+        }
+        const double l = lw[jj];                                           // rewritten only after the next component's first barrier
+#pragma unroll
+        for (int q = 0; q < 4; ++q) N[m][q] = l + -0.5 * acc[q];
+    }
+    const int j = j0 + jj;
+    if (j >= J) return;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int t = t0 + tg + 8 * q;
+        if (t >= T) continue;
+        double mx = N[0][q];
+#pragma unroll
+        for (int m = 1; m < M; ++m) mx = fmax(mx, N[m][q]);
+        double e = mx;
+        if (mx != al_ninf()) {
+            double s = exp(N[0][q] - mx);
+#pragma unroll
+            for (int m = 1; m < M; ++m) s += exp(N[m][q] - mx);
+            e = mx + log(s);
+        }
+        E[(size_t)b * lde_b + (size_t)t * lde_t + j] = e;
+        if (resp) {
+            double* rr = resp + (size_t)b * ldr_b + (size_t)t * ldr_t + (size_t)j * ldr_j;
+#pragma unroll
+            for (int m = 0; m < M; ++m) rr[m] = mx != al_ninf() ? exp(N[m][q] - e) : 0.0;
+        }
+    }
+}
+extern "C" int fs2_align_max_mixtures(void) { return AL_MAX_MIX; }
+
+extern "C" int fs2_align_emit_gmm(const double* x, long ldx_b, long ldx_t, const int32_t* lens, const int32_t* jlens,
+                                  const int32_t* sid, long ldg, const double* w, const double* mu, const double* var, int n_classes,
+                                  int M, int D, double* E, long lde_b, long lde_t, double* resp, long ldr_b, long ldr_t, long ldr_j,
+                                  int B, int Tmax, int Jmax, hipStream_t stream) {
+    FS2_CHECK_ARG(x && lens && jlens && sid && w && mu && var && E, "align_emit_gmm: null pointer");
+    FS2_CHECK_ARG(M >= 1 && M <= AL_MAX_MIX, "align_emit_gmm: %d mixture components, supported are 1..%d", M, AL_MAX_MIX);
+    FS2_CHECK_ARG(B >= 0 && B <= 65535 && Tmax >= 0 && Tmax <= 65535 * AL_TILE && Jmax >= 0 && D > 0 && n_classes > 0 && ldx_t >= D &&
+                      ldx_b >= (long)Tmax * ldx_t && lde_t >= Jmax && lde_b >= (long)Tmax * lde_t && ldg >= Jmax,
+                  "align_emit_gmm: bad shape B=%d Tmax=%d Jmax=%d D=%d classes=%d", B, Tmax, Jmax, D, n_classes);
+    FS2_CHECK_ARG(!resp || (ldr_j >= M && ldr_t >= (long)Jmax * ldr_j && ldr_b >= (long)Tmax * ldr_t),
+                  "align_emit_gmm: bad responsibility strides %ld %ld %ld", ldr_b, ldr_t, ldr_j);
+    FS2_CHECK_ARG(Jmax <= AL_MAX_STATES, "align_emit_gmm: %d states exceed the supported maximum of %d", Jmax, AL_MAX_STATES);
+    if (B == 0 || Tmax == 0 || Jmax == 0) return FS2_OK;
+    const dim3 grid(fs2_cdiv(Jmax, AL_TILE), fs2_cdiv(Tmax, AL_TILE), B);
+#define AL_GMM(MM)                                                                                                                  \
+    case MM:                                                                                                                        \
+        align_emit_gmm_kernel<MM><<<grid, 256, 0, stream>>>(x, ldx_b, ldx_t, lens, jlens, sid, ldg, w, mu, var, n_classes, D, E, lde_b, \
+                                                            lde_t, resp, ldr_b, ldr_t, ldr_j, Tmax, Jmax);                          \
+        break
+    switch (M) {
+        AL_GMM(1); AL_GMM(2); AL_GMM(3); AL_GMM(4); AL_GMM(5); AL_GMM(6); AL_GMM(7); AL_GMM(8);
+    }
+#undef AL_GMM
+    FS2_CHECK_LAUNCH("align_emit_gmm");
     return FS2_OK;
 }
 
@@ -493,6 +621,76 @@ extern "C" int fs2_align_stats(const double* gamma, long ldo_b, long ldo_t, cons
     align_stats_kernel<<<dim3(fs2_cdiv(D, AL_TILE), fs2_cdiv(Jmax, AL_TILE), B), 256, 0, stream>>>(
         gamma, ldo_b, ldo_t, x, ldx_b, ldx_t, lens, jlens, D, partials, ldp_b, ldp_j, Tmax, Jmax);
     FS2_CHECK_LAUNCH("align_stats");
+    return FS2_OK;
+}
+
+// The mixture statistics: rows are (j, m) = row / M, row % M, up to 8 x 1024 of them, and g = gamma[b][t][j] resp[b][t][j][m] is
+// formed while a frame block is staged, so no product of the two ever lies in HBM.  A lane stages the same row of every frame
+// (k & 31 = tid & 31), so its (j, m) is computed once.  Tiles, lane map and the ascending-t sums are align_stats_kernel's.
+__global__ void __launch_bounds__(256) align_stats_gmm_kernel(const double* __restrict__ gamma, long ldo_b, long ldo_t,
+                                                              const double* __restrict__ resp, long ldr_b, long ldr_t, long ldr_j,
+                                                              const double* __restrict__ x, long ldx_b, long ldx_t,
+                                                              const int32_t* __restrict__ lens, const int32_t* __restrict__ jlens,
+                                                              int M, int D, double* __restrict__ P, long ldp_b, long ldp_r, int Tmax,
+                                                              int Jmax) {
+    __shared__ double gs[AL_TILE][AL_TILE + 1], xs[AL_TILE][AL_TILE + 1];
+    const int b = blockIdx.z, T = al_len(lens, b, Tmax), J = al_len(jlens, b, Jmax), R = J * M;
+    const int d0 = blockIdx.x * AL_TILE, r0 = blockIdx.y * AL_TILE, tid = threadIdx.x;
+    if (r0 >= R) return;
+    const int dd = tid & 31, jg = tid >> 5;
+    const int srow = r0 + dd, sj = srow / M, sm = srow - sj * M;           // the row this lane stages
+    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    const double* gb = gamma + (size_t)b * ldo_b + sj;
+    const double* rb = resp + (size_t)b * ldr_b + (size_t)sj * ldr_j + sm;
+    const double* xb = x + (size_t)b * ldx_b;
+    for (int t0 = 0; t0 < T; t0 += AL_TILE) {
+        __syncthreads();
+        for (int k = tid; k < AL_TILE * AL_TILE; k += 256) {
+            const int r = k >> 5, t = t0 + r;
+            gs[r][dd] = (t < T && srow < R) ? gb[(size_t)t * ldo_t] * rb[(size_t)t * ldr_t] : 0.0;
+            xs[r][dd] = (t < T && d0 + dd < D) ? xb[(size_t)t * ldx_t + d0 + dd] : 0.0;
+        }
+        __syncthreads();
+        const int n = min(AL_TILE, T - t0);
+        for (int r = 0; r < n; ++r) {
+            const double xv = xs[r][dd], x2 = xv * xv;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double g = gs[r][jg + 8 * q];
+                s0[q] += g;
+                s1[q] += g * xv;
+                s2[q] += g * x2;
+            }
+        }
+    }
+    const int d = d0 + dd;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = r0 + jg + 8 * q;
+        if (row >= R) continue;
+        double* pr = P + (size_t)b * ldp_b + (size_t)row * ldp_r;
+        if (blockIdx.x == 0 && dd == 0) pr[0] = s0[q];
+        if (d < D) {
+            pr[1 + d] = s1[q];
+            pr[1 + D + d] = s2[q];
+        }
+    }
+}
+extern "C" int fs2_align_stats_gmm(const double* gamma, long ldo_b, long ldo_t, const double* resp, long ldr_b, long ldr_t, long ldr_j,
+                                   const double* x, long ldx_b, long ldx_t, const int32_t* lens, const int32_t* jlens, int M, int D,
+                                   double* partials, long ldp_b, long ldp_r, int B, int Tmax, int Jmax, hipStream_t stream) {
+    FS2_CHECK_ARG(gamma && resp && x && lens && jlens && partials, "align_stats_gmm: null pointer");
+    FS2_CHECK_ARG(M >= 1 && M <= AL_MAX_MIX, "align_stats_gmm: %d mixture components, supported are 1..%d", M, AL_MAX_MIX);
+    FS2_CHECK_ARG(B >= 0 && B <= 65535 && Tmax >= 0 && Jmax >= 0 && D > 0 && ldo_t >= Jmax && ldo_b >= (long)Tmax * ldo_t && ldx_t >= D &&
+                      ldx_b >= (long)Tmax * ldx_t && ldp_r >= 1 + 2 * D && ldp_b >= (long)Jmax * M * ldp_r && ldr_j >= M &&
+                      ldr_t >= (long)Jmax * ldr_j && ldr_b >= (long)Tmax * ldr_t,
+                  "align_stats_gmm: bad shape B=%d Tmax=%d Jmax=%d M=%d D=%d", B, Tmax, Jmax, M, D);
+    FS2_CHECK_ARG((long)Jmax * M <= (long)AL_MAX_STATES * AL_MAX_MIX, "align_stats_gmm: %ld rows exceed the supported maximum of %d",
+                  (long)Jmax * M, AL_MAX_STATES * AL_MAX_MIX);
+    if (B == 0 || Jmax == 0) return FS2_OK;
+    align_stats_gmm_kernel<<<dim3(fs2_cdiv(D, AL_TILE), fs2_cdiv(Jmax * M, AL_TILE), B), 256, 0, stream>>>(
+        gamma, ldo_b, ldo_t, resp, ldr_b, ldr_t, ldr_j, x, ldx_b, ldx_t, lens, jlens, M, D, partials, ldp_b, ldp_r, Tmax, Jmax);
+    FS2_CHECK_LAUNCH("align_stats_gmm");
     return FS2_OK;
 }
 

@@ -428,6 +428,14 @@ int fs2_align_feats(const float* mel, long ldm_b, long ldm_c, const int32_t* len
 int fs2_align_emit(const double* x, long ldx_b, long ldx_t, const int32_t* lens, const int32_t* jlens, const int32_t* sid, long ldg,
                    const double* mu, const double* var, int n_classes, int D, double* E, long lde_b, long lde_t, int B, int Tmax,
                    int Jmax, fs2_stream_t stream);
+/* Mixture emissions: component m of class c is row c * M + m of w [n_classes * M], mu and var [n_classes * M][D], 1 <= M <=
+ * fs2_align_max_mixtures() (8; more is FS2_EINVAL before any launch).  N_m = log w_m - 1/2 sum_d (...), log 0 = -inf;
+ * E[b][t][j] = mx + log(sum_m exp(N_m - mx)), mx = max_m N_m, over ascending m; resp[b][t][j][m] = exp(N_m - E) (strides ldr_b,
+ * ldr_t, ldr_j, m contiguous) unless resp is NULL.  With M = 1 and w = 1, E has the bits fs2_align_emit writes. */
+int fs2_align_max_mixtures(void);
+int fs2_align_emit_gmm(const double* x, long ldx_b, long ldx_t, const int32_t* lens, const int32_t* jlens, const int32_t* sid, long ldg,
+                       const double* w, const double* mu, const double* var, int n_classes, int M, int D, double* E, long lde_b,
+                       long lde_t, double* resp, long ldr_b, long ldr_t, long ldr_j, int B, int Tmax, int Jmax, fs2_stream_t stream);
 /* log-domain forward recursion over the arcs self, next (j - 1) and skip[b][j] -> alpha, loglik[b] over the end states */
 int fs2_align_forward(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
                       long ldg, const int32_t* alt, double* alpha, long lda_b, long lda_t, double* loglik, int B, int Tmax, int Jmax,
@@ -440,6 +448,11 @@ int fs2_align_backward(const double* E, long lde_b, long lde_t, const int32_t* l
 int fs2_align_stats(const double* gamma, long ldo_b, long ldo_t, const double* x, long ldx_b, long ldx_t, const int32_t* lens,
                     const int32_t* jlens, int D, double* partials, long ldp_b, long ldp_j, int B, int Tmax, int Jmax,
                     fs2_stream_t stream);
+/* partials[b][j * M + m] = sum_t gamma[b][t][j] * resp[b][t][j][m] * {1, x, x^2} (row stride ldp_r), ascending t; the product of
+ * gamma and resp is formed on the chip.  Jmax * M may reach 8192. */
+int fs2_align_stats_gmm(const double* gamma, long ldo_b, long ldo_t, const double* resp, long ldr_b, long ldr_t, long ldr_j,
+                        const double* x, long ldx_b, long ldx_t, const int32_t* lens, const int32_t* jlens, int M, int D,
+                        double* partials, long ldp_b, long ldp_r, int B, int Tmax, int Jmax, fs2_stream_t stream);
 /* sums[c][0..cols) = (accumulate ? sums[c] : 0) + the rows items[offs[c] .. offs[c + 1]) of partials (as [n_rows][ldp_j]), in list order */
 int fs2_align_reduce(const double* partials, long ldp_j, long n_rows, const int32_t* offs, const int32_t* items, int n_classes,
                      int cols, double* sums, int accumulate, fs2_stream_t stream);
