@@ -15,6 +15,9 @@ if __name__ == "__main__":
     parser.add_argument("--iters", type=int, default=12, help="Baum-Welch passes after the flat start")
     parser.add_argument("--mixtures", type=int, default=1, help="Gaussian mixture components per state, grown by splitting (1..8)")
     parser.add_argument("--mix_iters", type=int, default=4, help="Baum-Welch passes after every split")
+    parser.add_argument("--lda", type=int, default=0, help="output dimensions of an LDA over spliced frames before the Gaussian stages (0: none)")
+    parser.add_argument("--splice", type=int, default=3, help="frames of context on either side that --lda splices (0..4)")
+    parser.add_argument("--lda_iters", type=int, default=4, help="Baum-Welch passes after the LDA transform")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -25,7 +28,7 @@ if __name__ == "__main__":
     try:
         written, skipped, history = build(config, device=args.device, states=args.states, iters=args.iters, overwrite=args.overwrite,
                                           batch_bytes=int(args.batch_gib * (1 << 30)), num_workers=args.num_workers, mixtures=args.mixtures,
-                                          mix_iters=args.mix_iters)
+                                          mix_iters=args.mix_iters, lda=args.lda, splice=args.splice, lda_iters=args.lda_iters)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))

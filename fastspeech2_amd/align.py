@@ -65,9 +65,39 @@ way (speakers, allophones, stress), its variance inflates until neighbouring pho
   `fit` returns the log-likelihood per frame of every pass of every stage, in order, and logs K_c per stage.  Decoding takes E from
   the mixture emission (no responsibilities); Viterbi and backtracking are unchanged.  Nothing of this has been measured against MFA.
 
+LDA (`lda` = k > 0; the default k = 0 is everything above, unchanged).  In HTK, Kaldi and MFA (`lda_mllt`) the stage after the
+monophones is a linear discriminant transform of spliced frames.  Neighbouring mel channels are strongly correlated (overlapping
+filters, a smooth envelope) and a diagonal Gaussian counts that shared variation once per channel; the other aligners decorrelate
+with a DCT and LDA, this one has had neither.
+  Switches.  `lda` = k output dimensions; `splice` = c frames of context on either side, 0..4, default 3; `lda_iters` passes after
+  the transform, default 4.  c = 3 and k = 40 are Kaldi's customary values: here a choice, not a measurement.
+  Spliced vector.  x is the feature matrix above; its first n_mel columns are the mean-removed static features.
+  y[t, (p + c) n_mel + m] = x[min(max(t + p, 0), T - 1), m] for p = -c..c, m < n_mel; D_s = n_mel (2 c + 1).  The deltas are not
+  spliced, the context replaces them.  1 <= k <= D_s <= `max_splice_dim()` (720); anything else is a ValueError (FS2_EINVAL at the
+  ABI) before any launch.
+  Statistics.  One extra pass with the single-Gaussian model the `iters` passes ended with, gamma its posteriors.  Per class c:
+  n_c = sum gamma, a_c = sum gamma y (the reduction above, on y).  Over all frames of all utterances: N the frame count, s = sum y,
+  S = sum y y^T.  Every frame's posteriors sum to 1, so the class sums and the totals describe the same mass.
+  Transform (host, numpy float64).  m = s / N;  S_T = S / N - m m^T;  mu_c = a_c / n_c for the classes with n_c >= 1;
+  S_B = sum_c n_c (mu_c - m)(mu_c - m)^T / N over those classes;  S_W = S_T - S_B + eps I, eps = 1e-8 trace(S_T) / D_s;
+  S_W = L L^T (Cholesky);  `eigh` of L^-1 S_B L^-T, the k largest eigenvalues in descending order, eigenvectors v;  P holds the rows
+  v^T L^-1, each sign-flipped so that its entry of largest magnitude is positive (the lowest index on ties);  o = P m.
+  z[t] = P y[t] - o; the within-class covariance of z is the identity.
+  Schedule.  (1) The flat start and the `iters` passes in x, exactly as above.  (2) The statistics pass and the transform.  (3) With
+  the same gamma, one set of class sums on z gives the first (mu, var) in z-space (Kaldi's single-pass retraining); the global mean
+  g and variance v of z follow from their total, a class with n < 1 starts at (g, v).  (4) The variance floor becomes 1e-2 v.
+  (5) `lda_iters` Baum-Welch passes on z.  (6) The mixture stages, if `mixtures` > 1, on z.  (7) Decoding takes its emissions from z.
+  `fit` returns the log-likelihood per frame of every pass as before, the statistics pass listed once between the passes in x and
+  those in z, and logs the k eigenvalues.
+  Sums.  S is summed over the lower triangle's 64 x 64 tiles with the fp64 matrix instruction, per chunk of padded frames (at most
+  32 chunks, their length a function of the batch shape alone), frames ascending; the chunks are added in ascending order, the
+  total is added to the table and mirrored, batch after batch in a fixed order.  Nothing of this has been measured against MFA,
+  which cannot be run here, and nothing of it has been timed.
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
-update runs on the host in numpy.  Two runs over one corpus write byte-identical TextGrids.
+update runs on the host in numpy.  Every sum's order is a function of the batch shape only.  Two runs over one corpus write
+byte-identical TextGrids.
 """
 import os
 import re
@@ -441,6 +471,113 @@ def reduce(P, G, n_classes, sums=None, index=None):
     return sums
 
 
+def max_splice_dim():
+    return _lib.load().fs2_align_max_splice_dim()
+
+
+def splice_dim(n_mel, context, k=None):
+    """D_s = n_mel (2 c + 1) after the checks of the module docstring: c in 0..4, D_s <= `max_splice_dim()`, 1 <= k <= D_s."""
+    n_mel, context = int(n_mel), int(context)
+    if not 0 <= context <= 4:
+        raise ValueError(f"splice must be 0..4 frames of context, got {context}")
+    Ds = n_mel * (2 * context + 1)
+    if n_mel < 1 or Ds > max_splice_dim():
+        raise ValueError(f"{n_mel} channels x {2 * context + 1} frames = {Ds} spliced dimensions, supported are 1..{max_splice_dim()}")
+    if k is not None and not 1 <= int(k) <= Ds:
+        raise ValueError(f"lda must be 1..{Ds} output dimensions (D_s), got {k}")
+    return Ds
+
+
+def splice(x, lens, n_mel, context, out=None):
+    """y (B, Tmax, n_mel (2 c + 1)) float64: the first n_mel columns of x (B, Tmax, >= n_mel) over the frames t - c .. t + c, clamped
+    at each utterance's own ends."""
+    _no_host(x=x, out=out)
+    x = _dev(x, torch.float64, "x")
+    B, Tmax, D = x.shape
+    Ds = splice_dim(n_mel, context)
+    if D < n_mel:
+        raise ValueError(f"x {tuple(x.shape)} has fewer than {n_mel} columns")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", x.device)
+    y = torch.empty(B, Tmax, Ds, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
+    if y.shape[0] != B or y.shape[1] < Tmax or y.shape[2] != Ds:
+        raise ValueError(f"out {tuple(y.shape)} is not ({B}, >= {Tmax}, {Ds})")
+    _lib.call("fs2_align_splice", x.data_ptr(), x.stride(0), x.stride(1), lens_d.data_ptr(), int(n_mel), int(context), y.data_ptr(),
+              y.stride(0), y.stride(1), B, Tmax, ops._stream())
+    return y
+
+
+def scatter(y, lens, s=None, S=None):
+    """(s (D_s,), S (D_s, D_s)) float64 on the device: sum y and sum y y^T over the valid frames of the batch, added to `s` and `S`
+    when they are given (both or neither).  S is exactly symmetric."""
+    _no_host(y=y, s=s, S=S)
+    y = _dev(y, torch.float64, "y")
+    B, Tmax, Ds = y.shape
+    if not 1 <= Ds <= max_splice_dim():
+        raise ValueError(f"{Ds} dimensions, supported are 1..{max_splice_dim()}")
+    if (s is None) != (S is None):
+        raise ValueError("s and S are given together or not at all")
+    if s is None:
+        s = torch.zeros(Ds, dtype=torch.float64, device=y.device)
+        S = torch.zeros(Ds, Ds, dtype=torch.float64, device=y.device)
+    s, S = _dev(s, torch.float64, "s", 1), _dev(S, torch.float64, "S", 2)
+    if s.shape[0] != Ds or tuple(S.shape) != (Ds, Ds):
+        raise ValueError(f"s {tuple(s.shape)} and S {tuple(S.shape)} do not fit y {tuple(y.shape)}")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", y.device)
+    n_ws = _lib.load().fs2_align_scatter_ws(B, Tmax, Ds)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float64, device=y.device)
+    _lib.call("fs2_align_scatter", y.data_ptr(), y.stride(0), y.stride(1), lens_d.data_ptr(), Ds, s.data_ptr(), S.data_ptr(), S.stride(0),
+              ws.data_ptr(), n_ws, B, Tmax, ops._stream())
+    return s, S
+
+
+def project(y, lens, P, o, out=None):
+    """z (B, Tmax, k) float64 = P y - o for P (k, D_s), o (k,) on the device."""
+    _no_host(y=y, P=P, o=o, out=out)
+    y = _dev(y, torch.float64, "y")
+    P, o = _dev(P, torch.float64, "P", 2).contiguous(), _dev(o, torch.float64, "o", 1).contiguous()
+    B, Tmax, Ds = y.shape
+    k = P.shape[0]
+    if P.shape[1] != Ds or o.shape[0] != k:
+        raise ValueError(f"y {tuple(y.shape)}, P {tuple(P.shape)} and o {tuple(o.shape)} do not fit together")
+    if not 1 <= k <= Ds <= max_splice_dim():
+        raise ValueError(f"{k} outputs of {Ds} dimensions, supported are 1 <= k <= D_s <= {max_splice_dim()}")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", y.device)
+    z = torch.empty(B, Tmax, k, dtype=torch.float64, device=y.device) if out is None else _dev(out, torch.float64, "out")
+    if z.shape[0] != B or z.shape[1] < Tmax or z.shape[2] != k:
+        raise ValueError(f"out {tuple(z.shape)} is not ({B}, >= {Tmax}, {k})")
+    _lib.call("fs2_align_project", y.data_ptr(), y.stride(0), y.stride(1), lens_d.data_ptr(), P.data_ptr(), o.data_ptr(), k, Ds,
+              z.data_ptr(), z.stride(0), z.stride(1), B, Tmax, ops._stream())
+    return z
+
+
+def lda_transform(n, a, N, s, S, k):
+    """The transform of the module docstring from the class sums n (C,), a (C, D_s) and the totals N, s (D_s,), S (D_s, D_s)
+    -> (P (k, D_s), o (k,), the k eigenvalues in descending order), numpy float64."""
+    n, a, s, S = (np.asarray(v, np.float64) for v in (n, a, s, S))
+    Ds = s.shape[0]
+    if a.ndim != 2 or a.shape != (n.shape[0], Ds) or S.shape != (Ds, Ds):
+        raise ValueError(f"n {n.shape}, a {a.shape}, s {s.shape} and S {S.shape} do not fit together")
+    if not 1 <= int(k) <= Ds:
+        raise ValueError(f"lda must be 1..{Ds} output dimensions (D_s), got {k}")
+    if not N > 0:
+        raise ValueError("no frames")
+    m = s / N
+    S_T = S / N - np.outer(m, m)
+    ok = n >= 1.0
+    d = a[ok] / n[ok, None] - m[None, :]
+    S_B = (d * n[ok, None]).T @ d / N
+    S_B = 0.5 * (S_B + S_B.T)
+    S_W = S_T - S_B + (1e-8 * np.trace(S_T) / Ds) * np.eye(Ds)
+    L = np.linalg.cholesky(0.5 * (S_W + S_W.T))
+    M = np.linalg.solve(L, np.linalg.solve(L, S_B).T)                      # L^-1 S_B L^-T (S_B is symmetric)
+    w, V = np.linalg.eigh(0.5 * (M + M.T))
+    top = np.argsort(-w, kind="stable")[:int(k)]
+    P = np.linalg.solve(L.T, V[:, top]).T                                  # rows v^T L^-1
+    lead = np.argmax(np.abs(P), axis=1)                                    # the first of the largest
+    P = P * np.where(P[np.arange(len(P)), lead] < 0.0, -1.0, 1.0)[:, None]
+    return P, P @ m, w[top]
+
+
 def viterbi(E, lens, G, out=None):
     """-> (backpointers uint8 like E, best end state (B,) int32, its score (B,) float64)."""
     E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
@@ -474,9 +611,10 @@ def backtrack(bp, lens, G, end):
 class Aligner:
     """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`.  With `mixtures` = M > 1
     `fit` goes on from that table to the mixture tables gw (n_classes, M), gmu, gvar (n_classes, M, dim) on the device and ncomp
-    (active components per class, numpy), and `align` decodes with those."""
+    (active components per class, numpy), and `align` decodes with those.  With `lda` = k > 0 `fit` goes on from the table in x to
+    the transform P (k, D_s), o (k,) and to tables of k columns (mu, var and the mixture tables), and `align` decodes in z."""
 
-    def __init__(self, n_classes, dim, states=2, device="cuda", mixtures=1, mix_iters=4, min_split_occ=40):
+    def __init__(self, n_classes, dim, states=2, device="cuda", mixtures=1, mix_iters=4, min_split_occ=40, lda=0, splice=3, lda_iters=4):
         self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
         if n_classes % states:
             raise ValueError(f"n_classes {n_classes} is not a multiple of states {states}")
@@ -485,6 +623,15 @@ class Aligner:
         self.var = torch.ones(n_classes, dim, dtype=torch.float64, device=self.device)
         self.floor = np.zeros(dim)
         self.mixtures, self.mix_iters, self.min_split_occ = int(mixtures), int(mix_iters), float(min_split_occ)
+        self.lda, self.splice, self.lda_iters, self.P, self.o = int(lda), int(splice), int(lda_iters), None, None
+        if self.lda != 0:
+            if dim % 2:
+                raise ValueError(f"dim {dim} is not 2 n_mel")
+            self.n_mel = dim // 2
+            self.splice_dim = splice_dim(self.n_mel, self.splice, self.lda)
+            if self.lda_iters < 0:
+                raise ValueError(f"lda_iters must not be negative, got {lda_iters}")
+            dim = self.lda                                                 # the mixture tables live in z
         if self.mixtures != 1:
             if not 1 <= self.mixtures <= max_mixtures():
                 raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
@@ -510,6 +657,9 @@ class Aligner:
         return lens, G
 
     def _set(self, mu, var):
+        if tuple(self.mu.shape) != mu.shape:                               # between the table in x and the table in z
+            self.mu = torch.empty(mu.shape, dtype=torch.float64, device=self.device)
+            self.var = torch.empty(mu.shape, dtype=torch.float64, device=self.device)
         self.mu.copy_(torch.from_numpy(np.ascontiguousarray(mu)))
         self.var.copy_(torch.from_numpy(np.ascontiguousarray(var)))
 
@@ -560,13 +710,74 @@ class Aligner:
             mu, var = m_step(s, mu, var, self.floor)
             self._set(mu, var)
             history.append(total / n_frames)
+        if self.lda:
+            prep, s, mu, var, more = self._fit_lda(prep, n_frames)
+            history += more
         if self.mixtures > 1:
             history += self._fit_mixtures(prep, n_frames, s[:, 0], mu, var)
         return history
 
+    def _posteriors(self, x, lens, G):
+        """gamma and the log-likelihoods of one batch under the single-Gaussian table."""
+        E = emit(x, lens, G, self.mu, self.var)
+        alpha, loglik = forward(E, lens, G)
+        return backward(E, lens, G, alpha, loglik), loglik
+
+    def _project(self, x, lens):
+        return project(splice(x, lens, self.n_mel, self.splice), lens, self.P, self.o)
+
+    def _fit_lda(self, prep, n_frames):
+        """Steps 2 to 5 of the LDA schedule from the table in x -> (prep with z for the features, the class sums of the last pass,
+        mu, var in z, the log-likelihood per frame of the statistics pass and of the passes in z)."""
+        C, Ds, k = self.n_classes, self.splice_dim, self.lda
+        sums, sv, sm, total = None, None, None, 0.0
+        for feats, lens, G, index in prep:                                 # the statistics pass
+            x = feats.to(self.device, non_blocking=True)
+            gamma, loglik = self._posteriors(x, lens, G)
+            y = splice(x, lens, self.n_mel, self.splice)
+            sums = reduce(stats(gamma, y, lens, G), G, C, sums, index)
+            sv, sm = scatter(y, lens, sv, sm)
+            total += float(np.sum(loglik.cpu().numpy()))
+            del gamma, y
+        history = [total / n_frames]
+        cs = sums.cpu().numpy()
+        P, o, eig = lda_transform(cs[:, 0], cs[:, 1:1 + Ds], float(n_frames), sv.cpu().numpy(), sm.cpu().numpy(), k)
+        print("lda: eigenvalues " + " ".join(f"{v:.4g}" for v in eig))
+        self.P = torch.from_numpy(np.ascontiguousarray(P)).to(self.device)
+        self.o = torch.from_numpy(np.ascontiguousarray(o)).to(self.device)
+
+        sums, zprep = None, []
+        for feats, lens, G, index in prep:                                 # the same gamma on z
+            x = feats.to(self.device, non_blocking=True)
+            gamma, _ = self._posteriors(x, lens, G)
+            z = self._project(x, lens)
+            sums = reduce(stats(gamma, z, lens, G), G, C, sums, index)
+            zprep.append((z.to(feats.device), lens, G, index))
+            del gamma
+        s = sums.cpu().numpy()
+        tot = s.sum(axis=0)
+        g_mean = tot[1:1 + k] / tot[0]
+        g_var = tot[1 + k:] / tot[0] - g_mean * g_mean
+        self.floor = VAR_FLOOR * g_var
+        mu, var = m_step(s, np.tile(g_mean, (C, 1)), np.tile(g_var, (C, 1)), self.floor)
+        self._set(mu, var)
+        for _ in range(self.lda_iters):
+            sums, total = None, 0.0
+            for zf, lens, G, index in zprep:
+                z = zf.to(self.device, non_blocking=True)
+                gamma, loglik = self._posteriors(z, lens, G)
+                sums = reduce(stats(gamma, z, lens, G), G, C, sums, index)
+                total += float(np.sum(loglik.cpu().numpy()))
+                del gamma
+            s = sums.cpu().numpy()
+            mu, var = m_step(s, mu, var, self.floor)
+            self._set(mu, var)
+            history.append(total / n_frames)
+        return zprep, s, mu, var, history
+
     def _fit_mixtures(self, prep, n_frames, occ0, mu, var):
         """The split stages k = 1 .. M - 1 from the one-component table (mu, var) whose last pass had the occupancies occ0."""
-        C, M, D = self.n_classes, self.mixtures, self.dim
+        C, M, D = self.n_classes, self.mixtures, mu.shape[1]
         w, gmu, gvar = np.zeros((C, M)), np.zeros((C, M, D)), np.ones((C, M, D))
         w[:, 0], gmu[:, 0], gvar[:, 0] = 1.0, mu, var
         ncomp, occ = np.ones(C, np.int64), np.zeros((C, M))
@@ -603,6 +814,10 @@ class Aligner:
         """Viterbi alignment of one ragged batch -> [frames per block (int32 numpy)] per utterance."""
         lens, G = self._prepare(feats, lens, graphs)
         x = feats.to(self.device, non_blocking=True)
+        if self.lda:
+            if self.P is None:
+                raise ValueError("an Aligner with lda has no transform before `fit`")
+            x = self._project(x, lens)
         E = emit(x, lens, G, self.mu, self.var) if self.mixtures == 1 else emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar)
         bp, end, _ = viterbi(E, lens, G)
         frames = backtrack(bp, lens, G, end).cpu().numpy()
@@ -610,18 +825,21 @@ class Aligner:
 
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
-def batches_by_bytes(frames, states, dim, budget, mixtures=1):
+def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0):
     """`ragged.greedy_batches` of (frames, states) under `budget` bytes of device buffers: E, alpha / gamma and backpointers (17 B per
-    cell), features, partials; with `mixtures` = M > 1 also the responsibilities (8 M B per cell) and M times the partials."""
+    cell), features, partials; with `mixtures` = M > 1 also the responsibilities (8 M B per cell) and M times the partials; with
+    `splice_dim` = D_s > 0 (LDA) also the spliced frames, D_s doubles per frame, and their partials while the statistics are taken
+    (the scatter workspace, at most 82 MB for any batch, is not counted)."""
     if mixtures == 1:
-        cost = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
+        base = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
     else:
-        cost = lambda n, T, J: n * (T * J * (17 + 8 * mixtures) + T * dim * 8 + J * mixtures * (1 + 2 * dim) * 8)  # noqa: E731
+        base = lambda n, T, J: n * (T * J * (17 + 8 * mixtures) + T * dim * 8 + J * mixtures * (1 + 2 * dim) * 8)  # noqa: E731
+    cost = base if not splice_dim else lambda n, T, J: base(n, T, J) + n * (T * splice_dim * 8 + J * (1 + 2 * splice_dim) * 8)
     return ragged.greedy_batches(list(zip(frames, states)), budget, cost)
 
 
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
-          batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4):
+          batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
     from . import audio as Audio
@@ -632,6 +850,7 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     raw, out_dir = config["path"]["raw_path"], os.path.join(config["path"]["preprocessed_path"], "TextGrid")
     pp = config["preprocessing"]
     sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
+    Ds = splice_dim(n_mel, splice, lda) if lda else 0                      # refuses a bad --lda / --splice before any work
     lexicon = read_lexicon(config["path"]["lexicon_path"])
     phone_ids = phone_table(lexicon)
     stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], n_mel, sr, pp["mel"]["mel_fmin"],
@@ -698,13 +917,13 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     frames, nstates = [it["x"].shape[0] for it in items], [len(it["graph"]["sid"]) for it in items]
     resident = sum(frames) * D * 8 <= resident_bytes
     packed = []
-    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures):
+    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures, Ds):
         feats = torch.zeros(len(batch), max(frames[i] for i in batch), D, dtype=torch.float64)
         for r, i in enumerate(batch):
             feats[r, :frames[i]] = items[i]["x"]
             items[i]["x"] = None
         packed.append((feats.to(dev) if resident else feats, [frames[i] for i in batch], [items[i]["graph"] for i in batch], batch))
-    aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters)
+    aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters, lda=lda, splice=splice, lda_iters=lda_iters)
     history = aligner.fit([p[:3] for p in packed], iters)
 
     written = 0

@@ -465,6 +465,27 @@ int fs2_align_viterbi(const double* E, long lde_b, long lde_t, const int32_t* le
 int fs2_align_backtrack(const uint8_t* bp, long ldp_b, long ldp_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
                         const int32_t* block, long ldg, const int32_t* end, int32_t* frames, int nbmax, int B, int Tmax, int Jmax,
                         fs2_stream_t stream);
+/* The LDA stage (csrc/fs2_align_lda.hip).  Spliced frames y [B][Tmax][D_s], D_s = n_mel (2 c + 1), strides ldy_b >= Tmax ldy_t,
+ * ldy_t >= D_s, in elements.  Limits, all FS2_EINVAL before any launch: 0 <= c <= 4, 1 <= k <= D_s <= fs2_align_max_splice_dim() (720).
+ * Nothing at t >= lens[b] is read or written.  No atomics. */
+int fs2_align_max_splice_dim(void);
+/* y[b][t][(p + c) n_mel + m] = x[b][min(max(t + p, 0), lens[b] - 1)][m], p = -c..c, m < n_mel: the first n_mel columns of x
+ * (ldx_t >= n_mel, ldx_b >= Tmax ldx_t), clamped at the utterance's own ends */
+int fs2_align_splice(const double* x, long ldx_b, long ldx_t, const int32_t* lens, int n_mel, int c, double* y, long ldy_b, long ldy_t,
+                     int B, int Tmax, fs2_stream_t stream);
+/* doubles of workspace fs2_align_scatter needs for a batch of this shape (0 for an empty batch or Ds outside 1..720); at most
+ * 32 (78 * 4096 + 768) */
+int fs2_align_scatter_ws(int B, int Tmax, int Ds);
+/* s[0..Ds) += sum y, S[Ds][Ds] (row stride lds >= Ds) += sum y y^T over the valid frames of the batch; the caller zeroes both before
+ * the first batch.  The padded rows b Tmax + t are cut into at most 32 chunks whose length depends on (B, Tmax) only; the lower
+ * triangle's 64 x 64 tiles are summed per chunk with v_mfma_f64_16x16x4_f64 in ascending t into ws, added in ascending chunk order,
+ * added to S and mirrored: S[i][j] and S[j][i] hold the same bits.  ws_doubles below fs2_align_scatter_ws() is FS2_EINVAL. */
+int fs2_align_scatter(const double* y, long ldy_b, long ldy_t, const int32_t* lens, int Ds, double* s, double* S, long lds, double* ws,
+                      long ws_doubles, int B, int Tmax, fs2_stream_t stream);
+/* z[b][t][q] = sum_d P[q][d] y[b][t][d] - o[q], q < K: P [K][Ds] contiguous, o [K], z strides ldz_b >= Tmax ldz_t, ldz_t >= K; the
+ * sum ascends in d (v_mfma_f64_16x16x4_f64, four d per step) */
+int fs2_align_project(const double* y, long ldy_b, long ldy_t, const int32_t* lens, const double* P, const double* o, int K, int Ds,
+                      double* z, long ldz_b, long ldz_t, int B, int Tmax, fs2_stream_t stream);
 
 /* ---- objective scoring: cepstra, dynamic time warping, F0 along the path (specification: fastspeech2_amd/metrics.py) ----
  * fp64 throughout, ragged batches of pairs: pair p has alens[p] reference frames (index i) and blens[p] synthesized frames (index j),
