@@ -18,6 +18,12 @@ if __name__ == "__main__":
     parser.add_argument("--lda", type=int, default=0, help="output dimensions of an LDA over spliced frames before the Gaussian stages (0: none)")
     parser.add_argument("--splice", type=int, default=3, help="frames of context on either side that --lda splices (0..4)")
     parser.add_argument("--lda_iters", type=int, default=4, help="Baum-Welch passes after the LDA transform")
+    parser.add_argument("--fmllr", type=int, default=0, choices=(0, 1),
+                        help="1: per-speaker fMLLR transforms after the LDA stage (needs at most 64 feature dimensions: --lda k, k <= 64)")
+    parser.add_argument("--fmllr_rounds", type=int, default=2, help="rounds of statistics, transform update and retraining")
+    parser.add_argument("--fmllr_iters", type=int, default=2, help="Baum-Welch passes after every transform update")
+    parser.add_argument("--fmllr_sweeps", type=int, default=20, help="row sweeps of every transform update")
+    parser.add_argument("--fmllr_min_frames", type=float, default=500, help="a speaker with fewer frames keeps its transform")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -28,7 +34,9 @@ if __name__ == "__main__":
     try:
         written, skipped, history = build(config, device=args.device, states=args.states, iters=args.iters, overwrite=args.overwrite,
                                           batch_bytes=int(args.batch_gib * (1 << 30)), num_workers=args.num_workers, mixtures=args.mixtures,
-                                          mix_iters=args.mix_iters, lda=args.lda, splice=args.splice, lda_iters=args.lda_iters)
+                                          mix_iters=args.mix_iters, lda=args.lda, splice=args.splice, lda_iters=args.lda_iters,
+                                          fmllr=args.fmllr, fmllr_rounds=args.fmllr_rounds, fmllr_iters=args.fmllr_iters,
+                                          fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))

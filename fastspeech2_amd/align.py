@@ -94,10 +94,48 @@ with a DCT and LDA, this one has had neither.
   total is added to the table and mirrored, batch after batch in a fixed order.  Nothing of this has been measured against MFA,
   which cannot be run here, and nothing of it has been timed.
 
+fMLLR (`fmllr` = 1; the default 0 is everything above, unchanged).  The stage after LDA in HTK, Kaldi (`train_sat`) and MFA (`sat`) is
+speaker adaptation: constrained MLLR (Gales 1998, "Maximum likelihood linear transformations for HMM-based speech recognition",
+section 3) estimates one affine feature transform per speaker by maximum likelihood and retrains the model in the normalised
+space, so that the Gaussians need not absorb vocal-tract and channel differences into their variances (the failure of the
+mixtures paragraph, one level up).  For a corpus of one speaker the same estimate is a global maximum-likelihood linear
+transform, the MLLT half of `lda_mllt`.
+  Notation.  f[t] is the D-dimensional feature the Gaussian stages see (z after `lda`, else x), xi[t] = (f[t], 1) has D + 1 entries.
+  Speaker s owns W_s = [A_s | b_s] (D, D + 1), at first [I | 0]; the adapted feature is fh[t] = W_s xi[t].  1 <= D <=
+  `max_fmllr_dim()` (64), anything else is a ValueError (FS2_EINVAL) before any launch: a speaker's statistics are D (D + 1)(D + 2)
+  doubles, 2.2 MB at D = 64 and 33 MB at D = 160, so with 80 mel channels `fmllr` needs `lda` = k <= 64.  `build` also refuses,
+  before any work, a corpus whose speaker tables (speakers x D (D + 1)(D + 2) x 8 bytes) exceed `resident_bytes`.
+  Frame weights.  With gamma the state posteriors under the current single-Gaussian table (mu, var), for frame t and dimension i:
+  c[t, i] = sum_j gamma[t, j] / var[sid_j, i],  h[t, i] = sum_j gamma[t, j] mu[sid_j, i] / var[sid_j, i], both over j ascending.
+  Statistics.  Per speaker s over all frames of all its utterances: beta_s = the frame count, G_s[i] = sum_t c[t, i] xi[t] xi[t]^T
+  (D + 1, D + 1), k_s[i] = sum_t h[t, i] xi[t] (D + 1).  xi is always taken from the unadapted f; gamma, mu and var come from the
+  current model evaluated on fh.
+  Update (host, numpy, `fmllr_update`).  A speaker with beta_s < `fmllr_min_frames` (default 500, Kaldi's value; here a choice) keeps
+  W_s.  Otherwise every G_s[i] is inverted once; if a `np.linalg.cholesky(G_s[i])` raises, the speaker keeps W_s and is reported.
+  Then `fmllr_sweeps` sweeps (default 20, a choice) over the rows i = 0 .. D - 1 in order:  p = (column i of A^-1, 0), A^-1 from
+  `np.linalg.inv` of the current A at every row;  a = p G^-1 p^T;  c = p G^-1 k^T;  alpha = the root of a alpha^2 + c alpha - beta = 0
+  with the larger beta log|alpha a + c| - a alpha^2 / 2, the '+' root on a tie;  row i of W becomes (alpha p + k) G^-1.  This is
+  Gales's row-by-row maximiser of beta log|det A| - 1/2 sum_i (w_i G_i w_i^T - 2 w_i k_i^T), which cannot decrease at any row step.
+  Schedule.  Every stage up to and including the `lda_iters` passes (without `lda`: the `iters` passes) runs unchanged.  Then
+  `fmllr_rounds` rounds (default 2, a choice), each: (a) a statistics pass: posteriors on fh, frame weights, accumulation; (b) the
+  update; (c) fh recomputed; (d) `fmllr_iters` Baum-Welch passes on fh (default 2, a choice) with the variance floor of the stage
+  before.  The mixture stages and decoding then run on fh with the transforms frozen; re-estimating the transforms under mixtures
+  is out of scope.  From the first statistics pass on `fit` reports per pass (sum_u loglik_u + T_u log|det A_s(u)|) / n_frames, so
+  the numbers stay comparable across the stage and the pass after an update does not report less than the statistics pass before
+  it.  `fit` prints one line per round: speakers adapted, speakers kept (too few frames / not positive definite), the mean
+  log|det A|.  `fit` and `align` take the speaker index of every utterance; with `fmllr` on, a missing list or an index that is
+  negative or outside the speakers `fit` saw is a ValueError.
+  Sums.  G_s[i] is summed over the lower triangle's 16 x 16 tiles with the fp64 matrix instruction, the frame its k index, c[t, i] xi[t]
+  one operand and xi[t] the other.  A speaker's utterances are taken in batch-row order, frames ascending; its padded frames are cut
+  into chunks (their length a function of the batch shape alone) whose partial sums are added in ascending chunk order, the total
+  is added to the table and mirrored (G_s[i] is exactly symmetric), batch after batch in the fixed order.  Tables of speakers with
+  no utterance in a batch are not touched by it.  Nothing of this has been measured against MFA, which cannot be run here, and
+  nothing of it has been timed.
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
-update runs on the host in numpy.  Every sum's order is a function of the batch shape only.  Two runs over one corpus write
-byte-identical TextGrids.
+update runs on the host in numpy.  Every sum's order is a function of the batch shape (for the speaker statistics: and of the
+batch's speaker list) only.  Two runs over one corpus write byte-identical TextGrids.
 """
 import os
 import re
@@ -578,6 +616,141 @@ def lda_transform(n, a, N, s, S, k):
     return P, P @ m, w[top]
 
 
+def max_fmllr_dim():
+    return _lib.load().fs2_align_max_fmllr_dim()
+
+
+def _fmllr_dim(D, what="fmllr"):
+    if not 1 <= int(D) <= max_fmllr_dim():
+        raise ValueError(f"{what}: {D} feature dimensions, supported are 1..{max_fmllr_dim()}")
+    return int(D)
+
+
+def _speaker_list(speakers, B, n_spk):
+    sp = np.asarray(list(speakers), dtype=np.int64).reshape(-1) if speakers is not None else None
+    if sp is None or sp.shape[0] != B:
+        raise ValueError(f"speakers must hold one speaker index for each of the {B} utterances")
+    if sp.size and (sp.min() < 0 or sp.max() >= n_spk):
+        raise ValueError(f"speaker index outside [0, {n_spk})")
+    return sp
+
+
+def fmllr_weights(gamma, lens, G, mu, var, out=None):
+    """The frame weights (c, h), each (B, Tmax, D) float64, from the posteriors gamma (B, Tmax, Jmax), the batch's Graphs and the
+    class tables mu, var (C, D); `out` = (c, h) may give the buffers."""
+    _no_host(gamma=gamma, mu=mu, var=var)
+    gamma, B, Tmax, _, lens_d = _check_scan(gamma, lens, G)
+    mu, var = _dev(mu, torch.float64, "mu", 2).contiguous(), _dev(var, torch.float64, "var", 2).contiguous()
+    D = _fmllr_dim(mu.shape[1], "fmllr_weights")
+    if mu.shape != var.shape or mu.shape[0] == 0:
+        raise ValueError(f"mu {tuple(mu.shape)} and var {tuple(var.shape)} do not fit together")
+    if out is None:
+        out = (torch.empty(B, Tmax, D, dtype=torch.float64, device=gamma.device), torch.empty(B, Tmax, D, dtype=torch.float64, device=gamma.device))
+    _no_host(c=out[0], h=out[1])
+    c, h = _dev(out[0], torch.float64, "c"), _dev(out[1], torch.float64, "h")
+    if c.shape[0] != B or c.shape[1] < Tmax or c.shape[2] != D or c.shape != h.shape or c.stride() != h.stride():
+        raise ValueError(f"out {tuple(c.shape)}, {tuple(h.shape)} is not twice ({B}, >= {Tmax}, {D}) with the same strides")
+    _lib.call("fs2_align_fmllr_weights", gamma.data_ptr(), gamma.stride(0), gamma.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.sid.data_ptr(), G.ldg, mu.data_ptr(), var.data_ptr(), mu.shape[0], D, c.data_ptr(), h.data_ptr(), c.stride(0), c.stride(1),
+              B, Tmax, G.Jmax, ops._stream())
+    return c, h
+
+
+def fmllr_accumulate(f, c, h, lens, speakers, n_spk, beta=None, G=None, k=None):
+    """(beta (n_spk,), G (n_spk, D, D + 1, D + 1), k (n_spk, D, D + 1)) float64 on the device: the speaker statistics of one batch
+    from the unadapted features f and the frame weights c, h (all (B, Tmax, D)), `speakers` one index per utterance (host); added
+    to `beta`, `G`, `k` when they are given (all or none).  G[s, i] is exactly symmetric; a speaker without utterances in the batch
+    keeps its tables."""
+    _no_host(f=f, c=c, h=h, beta=beta, G=G, k=k)
+    f, c, h = _dev(f, torch.float64, "f"), _dev(c, torch.float64, "c"), _dev(h, torch.float64, "h")
+    B, Tmax, D = f.shape
+    _fmllr_dim(D, "fmllr_accumulate")
+    if c.shape[0] != B or c.shape[1] < Tmax or c.shape[2] != D or c.shape != h.shape or c.stride() != h.stride():
+        raise ValueError(f"c {tuple(c.shape)} and h {tuple(h.shape)} do not fit f {tuple(f.shape)}")
+    n_spk = int(n_spk)
+    if n_spk < 1:
+        raise ValueError(f"n_spk must be at least 1, got {n_spk}")
+    sp = _speaker_list(speakers, B, n_spk)
+    if (beta is None) != (G is None) or (beta is None) != (k is None):
+        raise ValueError("beta, G and k are given together or not at all")
+    if beta is None:
+        beta = torch.zeros(n_spk, dtype=torch.float64, device=f.device)
+        G = torch.zeros(n_spk, D, D + 1, D + 1, dtype=torch.float64, device=f.device)
+        k = torch.zeros(n_spk, D, D + 1, dtype=torch.float64, device=f.device)
+    beta, G, k = _dev(beta, torch.float64, "beta", 1), _dev(G, torch.float64, "G", 4), _dev(k, torch.float64, "k", 3)
+    if tuple(beta.shape) != (n_spk,) or tuple(G.shape) != (n_spk, D, D + 1, D + 1) or tuple(k.shape) != (n_spk, D, D + 1) or \
+            not (beta.is_contiguous() and G.is_contiguous() and k.is_contiguous()):
+        raise ValueError(f"beta {tuple(beta.shape)}, G {tuple(G.shape)}, k {tuple(k.shape)} are not the contiguous tables of {n_spk} "
+                         f"speakers in {D} dimensions")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", f.device)
+    offs = np.zeros(n_spk + 1, np.int64)                                   # CSR speaker -> batch rows, in batch-row order
+    np.cumsum(np.bincount(sp, minlength=n_spk), out=offs[1:])
+    rows = np.argsort(sp, kind="stable")
+    offs_d = torch.from_numpy(offs.astype(np.int32)).to(f.device)
+    rows_d = torch.from_numpy(rows.astype(np.int32)).to(f.device)
+    n_ws = _lib.load().fs2_align_fmllr_accum_ws(B, Tmax, D)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float64, device=f.device)
+    _lib.call("fs2_align_fmllr_accum", f.data_ptr(), f.stride(0), f.stride(1), c.data_ptr(), h.data_ptr(), c.stride(0), c.stride(1),
+              lens_d.data_ptr(), offs_d.data_ptr(), rows_d.data_ptr(), n_spk, D, beta.data_ptr(), G.data_ptr(), k.data_ptr(),
+              ws.data_ptr(), n_ws, B, Tmax, ops._stream())
+    return beta, G, k
+
+
+def fmllr_apply(f, lens, W, speakers, out=None):
+    """fh (B, Tmax, D) float64 = W[speaker] (f, 1) for W (n_spk, D, D + 1) on the device, `speakers` one index per utterance (host)."""
+    _no_host(f=f, W=W, out=out)
+    f, W = _dev(f, torch.float64, "f"), _dev(W, torch.float64, "W").contiguous()
+    B, Tmax, D = f.shape
+    _fmllr_dim(D, "fmllr_apply")
+    if W.shape[0] < 1 or tuple(W.shape[1:]) != (D, D + 1):
+        raise ValueError(f"W {tuple(W.shape)} is not (n_spk, {D}, {D + 1})")
+    sp = _speaker_list(speakers, B, W.shape[0])
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", f.device)
+    fh = torch.empty(B, Tmax, D, dtype=torch.float64, device=f.device) if out is None else _dev(out, torch.float64, "out")
+    if fh.shape[0] != B or fh.shape[1] < Tmax or fh.shape[2] != D:
+        raise ValueError(f"out {tuple(fh.shape)} is not ({B}, >= {Tmax}, {D})")
+    spk_d = torch.from_numpy(sp.astype(np.int32)).to(f.device)
+    _lib.call("fs2_align_fmllr_apply", f.data_ptr(), f.stride(0), f.stride(1), lens_d.data_ptr(), W.data_ptr(), spk_d.data_ptr(),
+              W.shape[0], D, fh.data_ptr(), fh.stride(0), fh.stride(1), B, Tmax, ops._stream())
+    return fh
+
+
+def fmllr_update(beta, G, k, W, min_frames=500.0, sweeps=20, trace=None):
+    """The update of the module docstring for all speakers at once: beta (S,), G (S, D, D + 1, D + 1), k (S, D, D + 1) and the current
+    W (S, D, D + 1) -> (W, status (S,) int8: 0 adapted, 1 kept for too few frames, 2 kept because a G_s[i] is not positive
+    definite), numpy float64.  `trace`, a list, receives a copy of the adapted speakers' W after every row step (the tests)."""
+    beta, G, k, W = (np.array(v, dtype=np.float64) for v in (beta, G, k, W))
+    if k.ndim != 3 or k.shape[2] != k.shape[1] + 1 or G.shape != k.shape + (k.shape[2],) or W.shape != k.shape or beta.shape != k.shape[:1]:
+        raise ValueError(f"beta {beta.shape}, G {G.shape}, k {k.shape} and W {W.shape} do not fit together")
+    S, D, P = k.shape
+    status = np.where(beta < min_frames, 1, 0).astype(np.int8)
+    Gi = np.zeros_like(G)
+    for s in np.nonzero(status == 0)[0]:
+        try:
+            np.linalg.cholesky(G[s])
+            Gi[s] = np.linalg.inv(G[s])
+        except np.linalg.LinAlgError:
+            status[s] = 2
+    ok = np.nonzero(status == 0)[0]
+    if ok.size == 0:
+        return W, status
+    Gi, kk, b, Wk = Gi[ok], k[ok], beta[ok], W[ok]
+    for _ in range(int(sweeps)):
+        for i in range(D):
+            p = np.concatenate([np.linalg.inv(Wk[:, :, :D])[:, :, i], np.zeros((len(ok), 1))], axis=1)
+            pG = np.einsum("np,npq->nq", p, Gi[:, i])
+            a, c = np.einsum("nq,nq->n", pG, p), np.einsum("nq,nq->n", pG, kk[:, i])
+            root = np.sqrt(c * c + 4.0 * a * b)
+            alpha = [(-c + root) / (2.0 * a), (-c - root) / (2.0 * a)]
+            gain = [b * np.log(np.abs(al * a + c)) - 0.5 * a * al * al for al in alpha]
+            al = np.where(gain[0] >= gain[1], alpha[0], alpha[1])          # the '+' root on a tie
+            Wk[:, i] = np.einsum("np,npq->nq", al[:, None] * p + kk[:, i], Gi[:, i])
+            if trace is not None:
+                trace.append(Wk.copy())
+    W[ok] = Wk
+    return W, status
+
+
 def viterbi(E, lens, G, out=None):
     """-> (backpointers uint8 like E, best end state (B,) int32, its score (B,) float64)."""
     E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
@@ -612,9 +785,12 @@ class Aligner:
     """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`.  With `mixtures` = M > 1
     `fit` goes on from that table to the mixture tables gw (n_classes, M), gmu, gvar (n_classes, M, dim) on the device and ncomp
     (active components per class, numpy), and `align` decodes with those.  With `lda` = k > 0 `fit` goes on from the table in x to
-    the transform P (k, D_s), o (k,) and to tables of k columns (mu, var and the mixture tables), and `align` decodes in z."""
+    the transform P (k, D_s), o (k,) and to tables of k columns (mu, var and the mixture tables), and `align` decodes in z.  With
+    `fmllr` = 1 `fit` goes on to the speaker transforms W (n_spk, D, D + 1) and to tables trained on the adapted features, and
+    `fit` and `align` take the speaker index of every utterance."""
 
-    def __init__(self, n_classes, dim, states=2, device="cuda", mixtures=1, mix_iters=4, min_split_occ=40, lda=0, splice=3, lda_iters=4):
+    def __init__(self, n_classes, dim, states=2, device="cuda", mixtures=1, mix_iters=4, min_split_occ=40, lda=0, splice=3, lda_iters=4,
+                 fmllr=0, fmllr_rounds=2, fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500):
         self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
         if n_classes % states:
             raise ValueError(f"n_classes {n_classes} is not a multiple of states {states}")
@@ -632,6 +808,17 @@ class Aligner:
             if self.lda_iters < 0:
                 raise ValueError(f"lda_iters must not be negative, got {lda_iters}")
             dim = self.lda                                                 # the mixture tables live in z
+        self.fmllr, self.W, self.n_spk = int(fmllr), None, 0
+        self.fmllr_rounds, self.fmllr_iters, self.fmllr_sweeps = int(fmllr_rounds), int(fmllr_iters), int(fmllr_sweeps)
+        self.fmllr_min_frames = float(fmllr_min_frames)
+        if self.fmllr != 0:
+            if self.fmllr != 1:
+                raise ValueError(f"fmllr must be 0 or 1, got {fmllr}")
+            if not 1 <= dim <= max_fmllr_dim():
+                raise ValueError(fmllr_dim_message(dim, self.lda))
+            if self.fmllr_rounds < 1 or self.fmllr_iters < 0 or self.fmllr_sweeps < 1 or self.fmllr_min_frames < 0:
+                raise ValueError(f"fmllr_rounds {fmllr_rounds} and fmllr_sweeps {fmllr_sweeps} must be at least 1, fmllr_iters "
+                                 f"{fmllr_iters} and fmllr_min_frames {fmllr_min_frames} not negative")
         if self.mixtures != 1:
             if not 1 <= self.mixtures <= max_mixtures():
                 raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
@@ -663,9 +850,23 @@ class Aligner:
         self.mu.copy_(torch.from_numpy(np.ascontiguousarray(mu)))
         self.var.copy_(torch.from_numpy(np.ascontiguousarray(var)))
 
-    def fit(self, batches, iters=12):
+    def _speakers(self, speakers, B, n_spk=None):
+        """The speaker indices of one batch, checked (None without fmllr)."""
+        if not self.fmllr:
+            return None
+        if speakers is None:
+            raise ValueError("an Aligner with fmllr needs the speaker index of every utterance (`speakers`)")
+        return _speaker_list(speakers, B, n_spk if n_spk is not None else np.iinfo(np.int32).max)
+
+    def fit(self, batches, iters=12, speakers=None):
         """batches: [(feats (B, Tmax, D) float64 on the device or the host, lens, graphs)].  Flat start, then `iters` Baum-Welch
-        passes (then, with mixtures, the split stages); returns the log-likelihood per frame of every pass."""
+        passes (then, with lda, fmllr and mixtures, their stages); returns the log-likelihood per frame of every pass.  `speakers`
+        (with fmllr): one list of speaker indices per batch."""
+        batches = list(batches)
+        if self.fmllr:
+            if speakers is None or len(speakers) != len(batches):
+                raise ValueError("an Aligner with fmllr needs one list of speaker indices per batch (`speakers`)")
+            speakers = [self._speakers(sp, b[0].shape[0]) for sp, b in zip(speakers, batches)]
         prep = []
         for feats, lens, graphs in batches:
             lens, G = self._prepare(feats, lens, graphs)
@@ -713,8 +914,12 @@ class Aligner:
         if self.lda:
             prep, s, mu, var, more = self._fit_lda(prep, n_frames)
             history += more
+        jac = 0.0
+        if self.fmllr:
+            prep, s, mu, var, more, jac = self._fit_fmllr(prep, speakers, n_frames, s, mu, var)
+            history += more
         if self.mixtures > 1:
-            history += self._fit_mixtures(prep, n_frames, s[:, 0], mu, var)
+            history += self._fit_mixtures(prep, n_frames, s[:, 0], mu, var, jac)
         return history
 
     def _posteriors(self, x, lens, G):
@@ -775,8 +980,55 @@ class Aligner:
             history.append(total / n_frames)
         return zprep, s, mu, var, history
 
-    def _fit_mixtures(self, prep, n_frames, occ0, mu, var):
-        """The split stages k = 1 .. M - 1 from the one-component table (mu, var) whose last pass had the occupancies occ0."""
+    def _fit_fmllr(self, prep, speakers, n_frames, s, mu, var):
+        """The fMLLR rounds from the single-Gaussian table (mu, var) on the features of `prep` -> (prep with the adapted features,
+        the class sums of the last pass, mu, var, the reported value of every pass, sum_u T_u log|det A_s(u)| of the final W)."""
+        C, D = self.n_classes, mu.shape[1]
+        S = self.n_spk = 1 + max((int(sp.max()) for sp in speakers if sp.size), default=0)
+        W = np.tile(np.eye(D, D + 1), (S, 1, 1))
+        self.W = torch.from_numpy(W).to(self.device)
+        spk_frames = np.zeros(S)
+        for (_, lens, _, _), sp in zip(prep, speakers):
+            np.add.at(spk_frames, sp, np.asarray(lens, np.float64))
+
+        def adapted():
+            return [(fmllr_apply(feats.to(self.device, non_blocking=True), lens, self.W, sp).to(feats.device), lens, G, index)
+                    for (feats, lens, G, index), sp in zip(prep, speakers)]
+        hprep, history, jac = adapted(), [], 0.0
+        for rnd in range(self.fmllr_rounds):
+            beta, Gs, ks, total = None, None, None, 0.0
+            for (feats, lens, G, _), (fh, _, _, _), sp in zip(prep, hprep, speakers):      # the statistics pass
+                gamma, loglik = self._posteriors(fh.to(self.device, non_blocking=True), lens, G)
+                c, h = fmllr_weights(gamma, lens, G, self.mu, self.var)
+                beta, Gs, ks = fmllr_accumulate(feats.to(self.device, non_blocking=True), c, h, lens, sp, S, beta, Gs, ks)
+                total += float(np.sum(loglik.cpu().numpy()))
+                del gamma, c, h
+            history.append((total + jac) / n_frames)
+            W, status = fmllr_update(beta.cpu().numpy(), Gs.cpu().numpy(), ks.cpu().numpy(), W, self.fmllr_min_frames, self.fmllr_sweeps)
+            del beta, Gs, ks
+            logdet = np.linalg.slogdet(W[:, :, :D])[1]
+            jac = float(np.dot(spk_frames, logdet))
+            print(f"fmllr: round {rnd + 1}, {int(np.sum(status == 0))} speakers adapted, {int(np.sum(status == 1))} kept (too few "
+                  f"frames), {int(np.sum(status == 2))} kept (not positive definite), mean log|det A| {float(np.mean(logdet)):.4g}")
+            self.W.copy_(torch.from_numpy(np.ascontiguousarray(W)))
+            hprep = adapted()
+            for _ in range(self.fmllr_iters):
+                sums, total = None, 0.0
+                for fh, lens, G, index in hprep:
+                    x = fh.to(self.device, non_blocking=True)
+                    gamma, loglik = self._posteriors(x, lens, G)
+                    sums = reduce(stats(gamma, x, lens, G), G, C, sums, index)
+                    total += float(np.sum(loglik.cpu().numpy()))
+                    del gamma
+                s = sums.cpu().numpy()
+                mu, var = m_step(s, mu, var, self.floor)
+                self._set(mu, var)
+                history.append((total + jac) / n_frames)
+        return hprep, s, mu, var, history, jac
+
+    def _fit_mixtures(self, prep, n_frames, occ0, mu, var, jac=0.0):
+        """The split stages k = 1 .. M - 1 from the one-component table (mu, var) whose last pass had the occupancies occ0; `jac`
+        (fmllr) is added to every pass's total log-likelihood."""
         C, M, D = self.n_classes, self.mixtures, mu.shape[1]
         w, gmu, gvar = np.zeros((C, M)), np.zeros((C, M, D)), np.ones((C, M, D))
         w[:, 0], gmu[:, 0], gvar[:, 0] = 1.0, mu, var
@@ -804,20 +1056,26 @@ class Aligner:
                 s = sums.cpu().numpy().reshape(C, M, 1 + 2 * D)
                 occ = s[:, :, 0]
                 w, gmu, gvar = m_step_gmm(s, w, gmu, gvar, ncomp, self.floor)
-                history.append(total / n_frames)
+                history.append((total + jac) / n_frames)
         for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
             dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
         self.ncomp = ncomp
         return history
 
-    def align(self, feats, lens, graphs):
-        """Viterbi alignment of one ragged batch -> [frames per block (int32 numpy)] per utterance."""
+    def align(self, feats, lens, graphs, speakers=None):
+        """Viterbi alignment of one ragged batch -> [frames per block (int32 numpy)] per utterance.  `speakers` (with fmllr): the
+        speaker index of every row."""
+        if self.fmllr and self.W is None:
+            raise ValueError("an Aligner with fmllr has no transforms before `fit`")
+        speakers = self._speakers(speakers, feats.shape[0], self.n_spk)
         lens, G = self._prepare(feats, lens, graphs)
         x = feats.to(self.device, non_blocking=True)
         if self.lda:
             if self.P is None:
                 raise ValueError("an Aligner with lda has no transform before `fit`")
             x = self._project(x, lens)
+        if self.fmllr:
+            x = fmllr_apply(x, lens, self.W, speakers)
         E = emit(x, lens, G, self.mu, self.var) if self.mixtures == 1 else emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar)
         bp, end, _ = viterbi(E, lens, G)
         frames = backtrack(bp, lens, G, end).cpu().numpy()
@@ -825,21 +1083,31 @@ class Aligner:
 
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
-def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0):
+def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmllr_dim=0):
     """`ragged.greedy_batches` of (frames, states) under `budget` bytes of device buffers: E, alpha / gamma and backpointers (17 B per
     cell), features, partials; with `mixtures` = M > 1 also the responsibilities (8 M B per cell) and M times the partials; with
     `splice_dim` = D_s > 0 (LDA) also the spliced frames, D_s doubles per frame, and their partials while the statistics are taken
-    (the scatter workspace, at most 82 MB for any batch, is not counted)."""
+    (the scatter workspace, at most 82 MB for any batch, is not counted); with `fmllr_dim` = D > 0 also the frame weights c, h and
+    the adapted frames, 3 D doubles per frame (the accumulation workspace, at most 141 MB and 16 B per utterance, is not counted)."""
     if mixtures == 1:
         base = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
     else:
         base = lambda n, T, J: n * (T * J * (17 + 8 * mixtures) + T * dim * 8 + J * mixtures * (1 + 2 * dim) * 8)  # noqa: E731
     cost = base if not splice_dim else lambda n, T, J: base(n, T, J) + n * (T * splice_dim * 8 + J * (1 + 2 * splice_dim) * 8)
+    if fmllr_dim:
+        lda_cost = cost
+        cost = lambda n, T, J: lda_cost(n, T, J) + n * T * 3 * fmllr_dim * 8               # noqa: E731
     return ragged.greedy_batches(list(zip(frames, states)), budget, cost)
 
 
+def fmllr_dim_message(dim, lda):
+    return (f"fmllr adapts at most {max_fmllr_dim()} feature dimensions (a speaker's statistics are D (D + 1)(D + 2) doubles), got {dim}"
+            + ("" if lda else f": with {dim // 2} mel channels --fmllr needs --lda k with k <= {max_fmllr_dim()}"))
+
+
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
-          batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4):
+          batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
+          fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
     from . import audio as Audio
@@ -851,15 +1119,22 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     pp = config["preprocessing"]
     sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
     Ds = splice_dim(n_mel, splice, lda) if lda else 0                      # refuses a bad --lda / --splice before any work
+    Df = (lda if lda else 2 * n_mel) if fmllr else 0
+    speakers = sorted(d for d in os.listdir(raw) if os.path.isdir(os.path.join(raw, d)))
+    if fmllr:
+        if not 1 <= Df <= max_fmllr_dim():
+            raise ValueError(fmllr_dim_message(Df, lda))
+        if len(speakers) * Df * (Df + 1) * (Df + 2) * 8 > resident_bytes:
+            raise ValueError(f"the fmllr statistics of {len(speakers)} speakers in {Df} dimensions take "
+                             f"{len(speakers) * Df * (Df + 1) * (Df + 2) * 8} bytes, more than resident_bytes = {resident_bytes}")
+    speaker_ids = {name: i for i, name in enumerate(speakers)}
     lexicon = read_lexicon(config["path"]["lexicon_path"])
     phone_ids = phone_table(lexicon)
     stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], n_mel, sr, pp["mel"]["mel_fmin"],
                               pp["mel"]["mel_fmax"])
 
     entries = []
-    for speaker in sorted(os.listdir(raw)):
-        if not os.path.isdir(os.path.join(raw, speaker)):
-            continue
+    for speaker in speakers:
         for name in sorted(os.listdir(os.path.join(raw, speaker))):
             if name.endswith(".wav") and os.path.exists(os.path.join(raw, speaker, name[:-4] + ".lab")):
                 entries.append((speaker, name[:-4]))
@@ -917,18 +1192,21 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     frames, nstates = [it["x"].shape[0] for it in items], [len(it["graph"]["sid"]) for it in items]
     resident = sum(frames) * D * 8 <= resident_bytes
     packed = []
-    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures, Ds):
+    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures, Ds, Df):
         feats = torch.zeros(len(batch), max(frames[i] for i in batch), D, dtype=torch.float64)
         for r, i in enumerate(batch):
             feats[r, :frames[i]] = items[i]["x"]
             items[i]["x"] = None
         packed.append((feats.to(dev) if resident else feats, [frames[i] for i in batch], [items[i]["graph"] for i in batch], batch))
-    aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters, lda=lda, splice=splice, lda_iters=lda_iters)
-    history = aligner.fit([p[:3] for p in packed], iters)
+    aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters, lda=lda, splice=splice, lda_iters=lda_iters,
+                      fmllr=fmllr, fmllr_rounds=fmllr_rounds, fmllr_iters=fmllr_iters, fmllr_sweeps=fmllr_sweeps,
+                      fmllr_min_frames=fmllr_min_frames)
+    spk_of = lambda batch: [speaker_ids[items[i]["entry"][0]] for i in batch] if fmllr else None    # noqa: E731
+    history = aligner.fit([p[:3] for p in packed], iters, [spk_of(p[3]) for p in packed] if fmllr else None)
 
     written = 0
     for feats, lens, graphs, batch in packed:
-        for i, fr in zip(batch, aligner.align(feats, lens, graphs)):
+        for i, fr in zip(batch, aligner.align(feats, lens, graphs, spk_of(batch))):
             e = items[i]["entry"]
             os.makedirs(os.path.join(out_dir, e[0]), exist_ok=True)
             wd, ph, xmax = intervals(items[i]["graph"], items[i]["words"], fr, hop, sr)

@@ -486,6 +486,34 @@ int fs2_align_scatter(const double* y, long ldy_b, long ldy_t, const int32_t* le
  * sum ascends in d (v_mfma_f64_16x16x4_f64, four d per step) */
 int fs2_align_project(const double* y, long ldy_b, long ldy_t, const int32_t* lens, const double* P, const double* o, int K, int Ds,
                       double* z, long ldz_b, long ldz_t, int B, int Tmax, fs2_stream_t stream);
+/* Speaker adaptation, constrained MLLR (csrc/fs2_align_fmllr.hip; specification: the "fMLLR" paragraph of fastspeech2_amd/align.py).
+ * f, c, h, out [B][Tmax][D] with strides ld*_b >= Tmax ld*_t, ld*_t >= D, in elements; xi = (f, 1) has D + 1 entries.  Limit,
+ * FS2_EINVAL before any launch: 1 <= D <= fs2_align_max_fmllr_dim() (64).  Nothing at t >= lens[b] or j >= jlens[b] is read or
+ * written.  No atomics.  Nothing of this has been timed. */
+int fs2_align_max_fmllr_dim(void);
+/* c[b][t][i] = sum_j gamma[b][t][j] / var[sid[b][j]][i], h[b][t][i] = sum_j gamma[b][t][j] mu[sid[b][j]][i] / var[sid[b][j]][i], j
+ * ascending; gamma [B][Tmax][Jmax] (ldg_t >= Jmax), sid [B][ldsid] as for fs2_align_emit, mu and var [n_classes][D] contiguous;
+ * c and h share their strides */
+int fs2_align_fmllr_weights(const double* gamma, long ldg_b, long ldg_t, const int32_t* lens, const int32_t* jlens, const int32_t* sid,
+                            long ldsid, const double* mu, const double* var, int n_classes, int D, double* c, double* h, long ldc_b,
+                            long ldc_t, int B, int Tmax, int Jmax, fs2_stream_t stream);
+/* doubles of workspace fs2_align_fmllr_accum needs for a batch of this shape (0 for an empty batch or D outside 1..64):
+ * 64 D (D + 1)(D + 2) for the partial tables and 2 B + 130 for the list of chunks */
+int fs2_align_fmllr_accum_ws(int B, int Tmax, int D);
+/* For every speaker s with rows in the CSR (offs [n_spk + 1], rows [offs[n_spk]], int32 on the device: the utterances b of speaker
+ * s are rows[offs[s] .. offs[s + 1]), every b at most once):  beta[s] += frames,  G[s][i] += sum_t c[b][t][i] xi xi^T
+ * ([n_spk][D][D + 1][D + 1] contiguous),  k[s][i] += sum_t h[b][t][i] xi ([n_spk][D][D + 1]), over the speaker's utterances in list
+ * order, t ascending; the caller zeroes the tables before the first batch, the tables of a speaker without rows are not touched.
+ * The speaker's padded rows are cut into chunks whose length depends on (B, Tmax) only; the lower triangle's 16 x 16 tiles are summed
+ * per chunk with v_mfma_f64_16x16x4_f64 in ascending t, the chunks are added in ascending order, the total is added to G and
+ * mirrored: G[s][i][p][q] and G[s][i][q][p] hold the same bits.  ws_doubles below fs2_align_fmllr_accum_ws() is FS2_EINVAL. */
+int fs2_align_fmllr_accum(const double* f, long ldf_b, long ldf_t, const double* c, const double* h, long ldc_b, long ldc_t,
+                          const int32_t* lens, const int32_t* offs, const int32_t* rows, int n_spk, int D, double* beta, double* G,
+                          double* k, double* ws, long ws_doubles, int B, int Tmax, fs2_stream_t stream);
+/* out[b][t][r] = sum_p W[spk[b]][r][p] f[b][t][p] + W[spk[b]][r][D], p ascending: W [n_spk][D][D + 1] contiguous, spk [B] int32 on
+ * the device, every entry in [0, n_spk) (an utterance whose entry is not is left unwritten) */
+int fs2_align_fmllr_apply(const double* f, long ldf_b, long ldf_t, const int32_t* lens, const double* W, const int32_t* spk, int n_spk,
+                          int D, double* out, long ldo_b, long ldo_t, int B, int Tmax, fs2_stream_t stream);
 
 /* ---- objective scoring: cepstra, dynamic time warping, F0 along the path (specification: fastspeech2_amd/metrics.py) ----
  * fp64 throughout, ragged batches of pairs: pair p has alens[p] reference frames (index i) and blens[p] synthesized frames (index j),
