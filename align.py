@@ -24,6 +24,13 @@ if __name__ == "__main__":
     parser.add_argument("--fmllr_iters", type=int, default=2, help="Baum-Welch passes after every transform update")
     parser.add_argument("--fmllr_sweeps", type=int, default=20, help="row sweeps of every transform update")
     parser.add_argument("--fmllr_min_frames", type=float, default=500, help="a speaker with fewer frames keeps its transform")
+    parser.add_argument("--triphones", type=int, default=0,
+                        help="leaves of a decision tree over word-internal triphone states, trained after the single-Gaussian stages (0: none)")
+    parser.add_argument("--tri_iters", type=int, default=4, help="Baum-Welch passes on the tied triphone states")
+    parser.add_argument("--tri_min_occ", type=float, default=100, help="frames either side of a tree split must keep")
+    parser.add_argument("--tri_min_gain", type=float, default=0.0, help="log-likelihood gain a tree split must exceed")
+    parser.add_argument("--questions", type=str, default=None,
+                        help="file of question sets, `name phone phone ...` per line (# is the word boundary); default: clustered from the data")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -36,7 +43,9 @@ if __name__ == "__main__":
                                           batch_bytes=int(args.batch_gib * (1 << 30)), num_workers=args.num_workers, mixtures=args.mixtures,
                                           mix_iters=args.mix_iters, lda=args.lda, splice=args.splice, lda_iters=args.lda_iters,
                                           fmllr=args.fmllr, fmllr_rounds=args.fmllr_rounds, fmllr_iters=args.fmllr_iters,
-                                          fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames)
+                                          fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames,
+                                          triphones=args.triphones, tri_iters=args.tri_iters, tri_min_occ=args.tri_min_occ,
+                                          tri_min_gain=args.tri_min_gain, questions=args.questions)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))

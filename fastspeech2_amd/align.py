@@ -132,6 +132,55 @@ transform, the MLLT half of `lda_mllt`.
   no utterance in a batch are not touched by it.  Nothing of this has been measured against MFA, which cannot be run here, and
   nothing of it has been timed.
 
+Triphones (`triphones` = L > 0 leaves; the default 0 is everything above, unchanged).  The stage between the monophones and the
+LDA in HTK, Kaldi and MFA (`monophone -> triphone -> lda_mllt -> sat`): coarticulation makes the first state of a phone depend on
+what precedes it and the last on what follows; a context-independent Gaussian absorbs that into its variance and mixtures can
+only answer it blindly, while the context is known from the transcript.  The triphones are word-internal (HTK's classic system)
+and tied by a likelihood decision tree (Young, Odell and Woodland 1994, "Tree-based state tying for high accuracy acoustic
+modelling").
+  Context (host, `triphone_contexts`).  A mandatory block of phone p in word w has the left context l = the phone of the previous
+  block if that block belongs to word w, else the boundary symbol `#`; r likewise from the next block.  Context never crosses a word
+  boundary, so it does not depend on whether an optional `sp` or `sil` is taken; the graph (`skip`, `block`, `alt`) is untouched, only
+  `sid` changes.  `sil`, `sp` and `spn` are context-independent: l = r = `#`, they are never a context and are never split.  A logical
+  state is (l, p, r, s); symbols are the phone ids and `#` = the number of phones.
+  Placement (a choice).  After the last single-Gaussian stage (the `iters` passes in x, the passes in z after `lda`, the passes on
+  the adapted features after `fmllr`) and before the mixtures: every earlier stage stays bit-identical and the tree is grown in
+  the best feature space the run has.  f is the feature those stages see, D its dimension, floor their variance floor.
+  Statistics pass.  Posteriors under the monophone table; partials with `fs2_align_stats`, reduced with `fs2_align_reduce` over an
+  index whose classes are the items: the distinct logical states seen in the corpus, numbered in sorted (p, s, l, r) order.  The
+  item sums (N_items, 1 + 2 D) stay on the device.  The pass is listed once in the history.  `build` refuses, before any work, a
+  table that may exceed `resident_bytes` (at most R S (R + 1)^2 + 3 S rows for R real phones).
+  Questions (host, numpy).  A question is (side, set of symbols); with n_sets sets, question q < n_sets asks whether l is in set q,
+  question n_sets <= q < 2 n_sets whether r is in set q - n_sets.  By default the sets come from a bottom-up clustering of the real
+  phones (the idea of Kaldi's `cluster-phones`): start from singletons; merge the pair of clusters with the smallest
+  sum_s (L_s(A) + L_s(B) - L_s(A u B)), L as below on the monophone sums pooled from the item sums (items ascending), a cluster
+  named by its lowest phone and ties going to the lowest pair; every singleton (ascending), every merged set (in merge order) except
+  the full set, and `{#}` are the 2 P - 1 sets.  `questions` = a file replaces them: one set per line, `name phone phone ...`, `#` the
+  boundary; an unknown phone is a ValueError.  At most `max_tree_sets()` (1024) sets, more is a ValueError (FS2_EINVAL).
+  Likelihood.  L(n, a, q) = -n / 2 sum_d (log(2 pi v_d) + 1), v_d = max(q_d / n - (a_d / n)^2, floor_d), d ascending; 0 for n = 0.
+  Tree.  One root per (p, s), node p S + s, holding that state's items; the roots of `sil`, `sp` and `spn` are leaves from the start.
+  A split of a node by question q is eligible when both sides have n >= `tri_min_occ` (default 100 frames, HTK's RO value, here a
+  choice; below 1 is a ValueError); its gain is (L(yes) + L(no)) - L(node); an ineligible split has gain -inf and no variance is
+  formed for it.  A node's best split is the largest gain, the lowest q on ties; the node splits if that gain exceeds
+  `tri_min_gain` (default 0, a choice).  The full tree is built level by level, all open nodes of a level in one launch
+  (`tree_gains`); the children of a level are numbered in ascending parent order, yes before no.
+  Budget.  The recorded splits are replayed on the host through a priority queue, the largest gain first, the lowest node number on
+  ties, until L leaves exist or no split is left: a node's best gain does not depend on other nodes, so this is best-first
+  splitting without one launch per split.  L below the number of roots (fixed leaves included) is a ValueError.  Leaves are
+  numbered in ascending node order.
+  Leaf table.  Each leaf gets (mu, var) by the update above on its pooled item sums (items ascending), starting from its root's
+  monophone parameters: a leaf with n < 1 (a root whose phone never occurs) keeps them.
+  Passes.  Graphs are rebuilt with `sid` = the leaf that the state's (p, s, l, r) reaches from its root; any triple reaches a leaf,
+  seen in training or not, so `align` works on new utterances.  The number of classes becomes the leaf count; `tri_iters`
+  Baum-Welch passes (default 4, a choice) with the floor unchanged, then the mixture stages on the leaves, decoding on the leaves.
+  `fit` logs the number of items, questions and leaves and the total gain, and keeps the tree as arrays over the nodes: the question,
+  the yes child, the no child, the leaf id, each -1 where there is none.
+  Sums.  For a node's items the yes-sums and the no-sums of every question are both accumulated directly with the fp64 matrix
+  instruction (a 0/1 matrix times the item table, the item its k index, ascending in steps of four); the order of every sum
+  depends on the node's item count and D alone, and a question's arithmetic does not depend on where it sits in the table: two
+  sets that part a node's items alike tie bit for bit and the lower index wins.  Nothing of this has been measured against MFA,
+  which cannot be run here, nothing is known about its gain on real speech, and nothing of it has been timed.
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
 update runs on the host in numpy.  Every sum's order is a function of the batch shape (for the speaker statistics: and of the
@@ -751,6 +800,203 @@ def fmllr_update(beta, G, k, W, min_frames=500.0, sweeps=20, trace=None):
     return W, status
 
 
+BOUNDARY = "#"
+
+
+def max_tree_sets():
+    return _lib.load().fs2_align_max_tree_sets()
+
+
+def triphone_contexts(graph, phone_ids, states=2):
+    """int32 (J, 4): per state j the ids (l, p, r, s) of its logical state.  l and r are phone ids or `len(phone_ids)`, the id of the
+    boundary symbol `#`: the phone of the neighbouring block when that block belongs to the same word, else `#`.  `sil`, `sp` and `spn`
+    are context-independent: they have l = r = `#` and are never a context."""
+    bnd, ci, blocks = len(phone_ids), (SIL, SP, SPN), graph["blocks"]
+    if len(graph["sid"]) != len(blocks) * states:
+        raise ValueError(f"a graph of {len(graph['sid'])} states does not have {states} states per block")
+
+    def neighbour(k, other):
+        if not 0 <= other < len(blocks) or blocks[k][0] in ci or blocks[k][1] < 0:
+            return bnd
+        p, w, _ = blocks[other]
+        return phone_ids[p] if w == blocks[k][1] and p not in ci else bnd
+    out = np.empty((len(blocks) * states, 4), np.int32)
+    for k, (p, _, _) in enumerate(blocks):
+        for s in range(states):
+            out[k * states + s] = (neighbour(k, k - 1), phone_ids[p], neighbour(k, k + 1), s)
+    return out
+
+
+def node_loglik(n, a, q, floor):
+    """L(n, a, q) = -n / 2 sum_d (log(2 pi v_d) + 1), v_d = max(q_d / n - (a_d / n)^2, floor_d), d ascending; 0 for n = 0."""
+    if not n > 0.0:
+        return 0.0
+    mu = a / n
+    return -0.5 * n * float(np.cumsum(np.log(2.0 * np.pi * np.maximum(q / n - mu * mu, floor)) + 1.0)[-1])
+
+
+def phone_questions(mono, phones, states, floor, n_symbols):
+    """The generated question sets of the module docstring from the pooled monophone sums `mono` (phones x states, 1 + 2 D): bottom-up
+    clustering of the real phones `phones` (ids) -> (names, member uint8 (2 P - 1, n_symbols)): the singletons in ascending order,
+    the merged sets in merge order without the full set, then `{#}` (symbol n_symbols - 1)."""
+    D = (mono.shape[1] - 1) // 2
+    phones = sorted(int(p) for p in phones)
+    lik = lambda t: sum(node_loglik(t[s, 0], t[s, 1:1 + D], t[s, 1 + D:], floor) for s in range(states))     # noqa: E731
+    sets = {p: [p] for p in phones}
+    tabs = {p: mono[p * states:(p + 1) * states] for p in phones}
+    liks = {p: lik(t) for p, t in tabs.items()}
+    cost = lambda i, j: liks[i] + liks[j] - lik(tabs[i] + tabs[j])                                          # noqa: E731
+    costs = {(i, j): cost(i, j) for i in phones for j in phones if i < j}
+    out = [[p] for p in phones]
+    while len(sets) > 2:
+        best = None
+        for pair in sorted(costs):                                         # the lowest pair on ties
+            if best is None or costs[pair] < costs[best]:
+                best = pair
+        i, j = best
+        sets[i], tabs[i] = sorted(sets[i] + sets.pop(j)), tabs[i] + tabs.pop(j)
+        liks[i] = lik(tabs[i])
+        del liks[j]
+        costs = {pr: c for pr, c in costs.items() if i not in pr and j not in pr}
+        for o in sets:
+            if o != i:
+                costs[(min(o, i), max(o, i))] = cost(min(o, i), max(o, i))
+        out.append(list(sets[i]))
+    out.append([n_symbols - 1])
+    member = np.zeros((len(out), n_symbols), np.uint8)
+    for k, ids in enumerate(out):
+        member[k, ids] = 1
+    return [f"g{k}" for k in range(len(out))], member
+
+
+def read_questions(path, phone_ids):
+    """A questions file, one set per line as `name phone phone ...` (`#` is the word boundary) -> (names, member uint8 (n_sets,
+    len(phone_ids) + 1)).  An unknown phone or a set without phones is a ValueError."""
+    names, rows = [], []
+    with open(path, encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts:
+                continue
+            if len(parts) < 2:
+                raise ValueError(f"{path}:{no}: the question {parts[0]} names no phone")
+            row = np.zeros(len(phone_ids) + 1, np.uint8)
+            for p in parts[1:]:
+                if p != BOUNDARY and p not in phone_ids:
+                    raise ValueError(f"{path}:{no}: unknown phone {p}")
+                row[len(phone_ids) if p == BOUNDARY else phone_ids[p]] = 1
+            names.append(parts[0])
+            rows.append(row)
+    if not rows:
+        raise ValueError(f"{path} holds no question")
+    return names, np.stack(rows)
+
+
+def tree_gains(sums, left, right, offs, items, member, floor, min_occ, full=False):
+    """For every node of the CSR list (offs (n_nodes + 1,), items: int32 indices into the item table `sums` (n_items, 1 + 2 D)) and
+    every question of `member` (n_sets, n_symbols) uint8 over the items' context symbols `left`, `right` (n_items,) int32:
+    -> (best question (n_nodes,) int32, -1 when no split is eligible; its gain (n_nodes,) float64) and, with `full`, the tables
+    gains and n_yes (n_nodes, 2 n_sets).  Everything on the device."""
+    _no_host(sums=sums, left=left, right=right, offs=offs, items=items, member=member, floor=floor)
+    sums, floor = _dev(sums, torch.float64, "sums", 2), _dev(floor, torch.float64, "floor", 1)
+    left, right = _dev(left, torch.int32, "left", 1), _dev(right, torch.int32, "right", 1)
+    offs, items = _dev(offs, torch.int32, "offs", 1), _dev(items, torch.int32, "items", 1)
+    member = _dev(member, torch.uint8, "member", 2)
+    n_items, cols = sums.shape
+    D = (cols - 1) // 2
+    if cols != 1 + 2 * D or D < 1 or floor.shape[0] != D or left.shape[0] != n_items or right.shape[0] != n_items or offs.shape[0] < 1:
+        raise ValueError(f"sums {tuple(sums.shape)}, floor {tuple(floor.shape)}, left {tuple(left.shape)}, right {tuple(right.shape)} and "
+                         f"offs {tuple(offs.shape)} do not fit together")
+    if not member.is_contiguous() or member.shape[1] < 1:
+        raise ValueError(f"member {tuple(member.shape)} must be a contiguous (n_sets, n_symbols) table")
+    if not 1 <= member.shape[0] <= max_tree_sets():
+        raise ValueError(f"{member.shape[0]} question sets, supported are 1..{max_tree_sets()}")
+    if not float(min_occ) >= 1.0:
+        raise ValueError(f"tri_min_occ must be at least 1, got {min_occ}")
+    n_nodes, Q = offs.shape[0] - 1, 2 * member.shape[0]
+    best_q = torch.empty(n_nodes, dtype=torch.int32, device=sums.device)
+    best_gain = torch.empty(n_nodes, dtype=torch.float64, device=sums.device)
+    gains = torch.empty(n_nodes, Q, dtype=torch.float64, device=sums.device) if full else None
+    n_yes = torch.empty(n_nodes, Q, dtype=torch.float64, device=sums.device) if full else None
+    _lib.call("fs2_align_tree_gains", sums.data_ptr(), sums.stride(0), n_items, left.data_ptr(), right.data_ptr(), offs.data_ptr(),
+              items.data_ptr(), items.shape[0], n_nodes, member.data_ptr(), member.shape[0], member.shape[1], floor.contiguous().data_ptr(),
+              D, float(min_occ), best_q.data_ptr(), best_gain.data_ptr(), gains.data_ptr() if full else None,
+              n_yes.data_ptr() if full else None, Q, ops._stream())
+    return (best_q, best_gain, gains, n_yes) if full else (best_q, best_gain)
+
+
+def tree_build(keys, roots, n_roots, fixed, member, gains_of, min_gain=0.0):
+    """The full tree of the module docstring, level by level.  keys (N, 4): the items' (p, s, l, r); roots (N,): the root p S + s of
+    every item; `fixed`: the roots that are leaves from the start; `gains_of([item index arrays])` -> (best question, its gain) per
+    node, one call per level -> dict(question, yes, no, gain, root: lists over the nodes, -1 / -inf where a node does not split;
+    items: the ascending item indices of every node)."""
+    keys, roots, n_sets = np.asarray(keys), np.asarray(roots), member.shape[0]
+    items = [np.nonzero(roots == m)[0] for m in range(n_roots)]
+    t = {"question": [-1] * n_roots, "yes": [-1] * n_roots, "no": [-1] * n_roots, "gain": [-np.inf] * n_roots,
+         "root": list(range(n_roots)), "items": items}
+    fixed = set(int(m) for m in fixed)
+    level = [m for m in range(n_roots) if m not in fixed and len(items[m])]
+    while level:
+        best_q, best_gain = gains_of([items[m] for m in level])
+        nxt = []
+        for m, q, g in zip(level, best_q, best_gain):
+            q, g = int(q), float(g)
+            if q < 0 or not g > min_gain:
+                continue
+            side = int(q >= n_sets)
+            ans = member[q - side * n_sets, keys[items[m], 3 if side else 2]] != 0
+            y = len(t["question"])
+            for it in (items[m][ans], items[m][~ans]):
+                t["question"].append(-1), t["yes"].append(-1), t["no"].append(-1), t["gain"].append(-np.inf)
+                t["root"].append(t["root"][m]), items.append(it)
+            t["question"][m], t["yes"][m], t["no"][m], t["gain"][m] = q, y, y + 1, g
+            nxt += [y, y + 1]
+        level = nxt
+    return t
+
+
+def tree_replay(tree, n_roots, budget):
+    """The leaf budget: the recorded splits replayed through a priority queue, the largest gain first, the lowest node number on ties,
+    until `budget` leaves exist or no split is left -> (question, yes, no, leaf: int32 arrays over the nodes of the full tree, -1
+    where a node was not split / is no leaf of the pruned tree; the total gain of the splits kept)."""
+    import heapq
+    if budget < n_roots:
+        raise ValueError(f"triphones = {budget} leaves is below the {n_roots} roots and fixed leaves")
+    n = len(tree["question"])
+    heap = [(-tree["gain"][m], m) for m in range(n_roots) if tree["question"][m] >= 0]
+    heapq.heapify(heap)
+    kept, live, leaves, total = np.zeros(n, bool), np.zeros(n, bool), n_roots, 0.0
+    live[:n_roots] = True
+    while heap and leaves < budget:
+        g, m = heapq.heappop(heap)
+        kept[m], leaves, total = True, leaves + 1, total - g
+        for c in (tree["yes"][m], tree["no"][m]):
+            live[c] = True
+            if tree["question"][c] >= 0:
+                heapq.heappush(heap, (-tree["gain"][c], c))
+    question = np.where(kept, np.array(tree["question"]), -1).astype(np.int32)
+    yes = np.where(kept, np.array(tree["yes"]), -1).astype(np.int32)
+    no = np.where(kept, np.array(tree["no"]), -1).astype(np.int32)
+    leaf = np.full(n, -1, np.int32)
+    is_leaf = live & ~kept
+    leaf[is_leaf] = np.arange(int(is_leaf.sum()), dtype=np.int32)
+    return question, yes, no, leaf, total
+
+
+def tree_leaves(question, yes, no, leaf, member, keys, states):
+    """The leaf id of every logical state keys (N, 4) = (p, s, l, r), seen in training or not: from root p S + s down the tree."""
+    keys = np.asarray(keys).reshape(-1, 4)
+    node, n_sets = keys[:, 0].astype(np.int64) * states + keys[:, 1], member.shape[0]
+    while True:
+        q = question[node]
+        go = q >= 0
+        if not go.any():
+            return leaf[node]
+        side = q >= n_sets
+        ans = member[np.where(go, q - side * n_sets, 0), np.where(side, keys[:, 3], keys[:, 2])] != 0
+        node = np.where(go, np.where(ans, yes[node], no[node]), node)
+
+
 def viterbi(E, lens, G, out=None):
     """-> (backpointers uint8 like E, best end state (B,) int32, its score (B,) float64)."""
     E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
@@ -787,14 +1033,17 @@ class Aligner:
     (active components per class, numpy), and `align` decodes with those.  With `lda` = k > 0 `fit` goes on from the table in x to
     the transform P (k, D_s), o (k,) and to tables of k columns (mu, var and the mixture tables), and `align` decodes in z.  With
     `fmllr` = 1 `fit` goes on to the speaker transforms W (n_spk, D, D + 1) and to tables trained on the adapted features, and
-    `fit` and `align` take the speaker index of every utterance."""
+    `fit` and `align` take the speaker index of every utterance.  With `triphones` = L > 0 (and `phone_ids`, the phone table) `fit`
+    goes on from the last single-Gaussian table to the decision tree `tree` (arrays over its nodes) and to tables over its leaves,
+    `n_classes` becomes the leaf count and `align` decodes on the leaves."""
 
     def __init__(self, n_classes, dim, states=2, device="cuda", mixtures=1, mix_iters=4, min_split_occ=40, lda=0, splice=3, lda_iters=4,
-                 fmllr=0, fmllr_rounds=2, fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500):
+                 fmllr=0, fmllr_rounds=2, fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100,
+                 tri_min_gain=0.0, questions=None, phone_ids=None):
         self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
         if n_classes % states:
             raise ValueError(f"n_classes {n_classes} is not a multiple of states {states}")
-        self.n_classes, self.dim, self.states = n_classes, dim, states
+        self.n_classes, self.n_mono, self.dim, self.states = n_classes, n_classes, dim, states
         self.mu = torch.zeros(n_classes, dim, dtype=torch.float64, device=self.device)
         self.var = torch.ones(n_classes, dim, dtype=torch.float64, device=self.device)
         self.floor = np.zeros(dim)
@@ -819,6 +1068,20 @@ class Aligner:
             if self.fmllr_rounds < 1 or self.fmllr_iters < 0 or self.fmllr_sweeps < 1 or self.fmllr_min_frames < 0:
                 raise ValueError(f"fmllr_rounds {fmllr_rounds} and fmllr_sweeps {fmllr_sweeps} must be at least 1, fmllr_iters "
                                  f"{fmllr_iters} and fmllr_min_frames {fmllr_min_frames} not negative")
+        self.triphones, self.tri_iters, self.tri_min_occ, self.tri_min_gain = int(triphones), int(tri_iters), float(tri_min_occ), float(tri_min_gain)
+        self.questions, self.phone_ids, self.tree = questions, phone_ids, None
+        if self.triphones != 0:
+            if phone_ids is None or len(phone_ids) * states != n_classes or any(p not in phone_ids for p in (SIL, SP, SPN)):
+                raise ValueError(f"an Aligner with triphones needs `phone_ids`, the phone table of its {n_classes // states} phones")
+            if self.triphones < n_classes:
+                raise ValueError(f"triphones = {triphones} leaves is below the {n_classes} roots and fixed leaves")
+            if not self.tri_min_occ >= 1.0:
+                raise ValueError(f"tri_min_occ must be at least 1, got {tri_min_occ}")
+            if self.tri_iters < 0 or not self.tri_min_gain >= 0.0:
+                raise ValueError(f"tri_iters {tri_iters} and tri_min_gain {tri_min_gain} must not be negative")
+            self.question_sets = read_questions(questions, phone_ids) if questions is not None else None
+            if self.question_sets is not None and len(self.question_sets[0]) > max_tree_sets():
+                raise ValueError(f"{len(self.question_sets[0])} question sets, supported are 1..{max_tree_sets()}")
         if self.mixtures != 1:
             if not 1 <= self.mixtures <= max_mixtures():
                 raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
@@ -863,6 +1126,7 @@ class Aligner:
         passes (then, with lda, fmllr and mixtures, their stages); returns the log-likelihood per frame of every pass.  `speakers`
         (with fmllr): one list of speaker indices per batch."""
         batches = list(batches)
+        self.n_classes, self.tree = self.n_mono, None                      # the stages before the tree train the monophones
         if self.fmllr:
             if speakers is None or len(speakers) != len(batches):
                 raise ValueError("an Aligner with fmllr needs one list of speaker indices per batch (`speakers`)")
@@ -917,6 +1181,9 @@ class Aligner:
         jac = 0.0
         if self.fmllr:
             prep, s, mu, var, more, jac = self._fit_fmllr(prep, speakers, n_frames, s, mu, var)
+            history += more
+        if self.triphones:
+            prep, s, mu, var, more = self._fit_triphones(prep, n_frames, mu, var, jac)
             history += more
         if self.mixtures > 1:
             history += self._fit_mixtures(prep, n_frames, s[:, 0], mu, var, jac)
@@ -1026,6 +1293,96 @@ class Aligner:
                 history.append((total + jac) / n_frames)
         return hprep, s, mu, var, history, jac
 
+    def _leaf_graph(self, graph):
+        """The graph with `sid` = the leaf of every state's logical state (the topology is untouched)."""
+        t = self.tree
+        ctx = triphone_contexts(graph, self.phone_ids, self.states)
+        sid = tree_leaves(t["question"], t["yes"], t["no"], t["leaf"], t["member"], ctx[:, [1, 3, 0, 2]], self.states)
+        return dict(graph, sid=sid.astype(np.int32))
+
+    def _fit_triphones(self, prep, n_frames, mu, var, jac=0.0):
+        """The triphone stage from the single-Gaussian monophone table (mu, var) on the features of `prep` -> (prep with the leaf
+        graphs, the leaf sums of the last pass, mu, var over the leaves, the reported value of the statistics pass and of the
+        `tri_iters` passes).  `jac` (fmllr) is added to every pass's total log-likelihood."""
+        S, C0, D = self.states, self.n_classes, mu.shape[1]
+        n_sym, cols = len(self.phone_ids) + 1, 1 + 2 * mu.shape[1]
+        code = lambda k: ((k[:, 0].astype(np.int64) * S + k[:, 1]) * n_sym + k[:, 2]) * n_sym + k[:, 3]     # noqa: E731
+        ctxs = [[triphone_contexts(g, self.phone_ids, S)[:, [1, 3, 0, 2]] for g in G.graphs] for _, _, G, _ in prep]
+        keys = np.unique(np.concatenate([k for b in ctxs for k in b]), axis=0)       # the items, sorted by (p, s, l, r)
+        codes, n_items = code(keys), len(keys)
+
+        sums, total = None, 0.0                                            # the statistics pass over the items
+        for (feats, lens, G, _), kb in zip(prep, ctxs):
+            x = feats.to(self.device, non_blocking=True)
+            gamma, loglik = self._posteriors(x, lens, G)
+            Gi = Graphs([dict(g, sid=np.searchsorted(codes, code(k)).astype(np.int32)) for g, k in zip(G.graphs, kb)], self.device)
+            sums = reduce(stats(gamma, x, lens, G), Gi, n_items, sums, Gi.index(n_items, G.ldg))
+            total += float(np.sum(loglik.cpu().numpy()))
+            del gamma
+        history = [(total + jac) / n_frames]
+
+        def pooled(classes, n):                                            # class sums of the item table, items ascending
+            order = np.argsort(classes, kind="stable")
+            offs = np.zeros(n + 1, np.int64)
+            np.cumsum(np.bincount(classes, minlength=n), out=offs[1:])
+            index = (torch.from_numpy(offs.astype(np.int32)).to(self.device), torch.from_numpy(order.astype(np.int32)).to(self.device))
+            return reduce(sums.view(1, n_items, cols), None, n, None, index).cpu().numpy()
+        roots = keys[:, 0].astype(np.int64) * S + keys[:, 1]
+        ci = sorted(self.phone_ids[p] for p in (SIL, SP, SPN))
+        if self.question_sets is not None:
+            names, member = self.question_sets
+        else:
+            names, member = phone_questions(pooled(roots, C0), [p for p in range(C0 // S) if p not in ci], S, self.floor, n_sym)
+        if not 1 <= len(names) <= max_tree_sets():
+            raise ValueError(f"{len(names)} question sets, supported are 1..{max_tree_sets()}")
+        left = torch.from_numpy(keys[:, 2].astype(np.int32)).to(self.device)
+        right = torch.from_numpy(keys[:, 3].astype(np.int32)).to(self.device)
+        member_d, floor_d = torch.from_numpy(member).to(self.device), torch.from_numpy(np.ascontiguousarray(self.floor)).to(self.device)
+
+        def gains_of(nodes):                                               # one launch per level
+            offs = np.zeros(len(nodes) + 1, np.int64)
+            np.cumsum([len(it) for it in nodes], out=offs[1:])
+            q, g = tree_gains(sums, left, right, torch.from_numpy(offs.astype(np.int32)).to(self.device),
+                              torch.from_numpy(np.concatenate(nodes).astype(np.int32)).to(self.device), member_d, floor_d, self.tri_min_occ)
+            return q.cpu().numpy(), g.cpu().numpy()
+        full = tree_build(keys, roots, C0, [p * S + st for p in ci for st in range(S)], member, gains_of, self.tri_min_gain)
+        question, yes, no, leaf, gain = tree_replay(full, C0, self.triphones)
+        n_leaves = int(leaf.max()) + 1
+        self.tree = {"question": question, "yes": yes, "no": no, "leaf": leaf, "member": member, "names": names, "gain": gain,
+                     "n_items": n_items, "n_leaves": n_leaves}
+        print(f"triphones: {n_items} items, {2 * len(names)} questions, {n_leaves} leaves, total gain {gain:.6g}")
+
+        item_leaf = tree_leaves(question, yes, no, leaf, member, keys, S)
+        leaf_root = np.zeros(n_leaves, np.int64)
+        leaf_root[leaf[leaf >= 0]] = np.array(full["root"])[leaf >= 0]
+        s = pooled(item_leaf.astype(np.int64), n_leaves)
+        mu, var = m_step(s, mu[leaf_root], var[leaf_root], self.floor)
+        del sums
+        self.n_classes = n_leaves
+        self._set(mu, var)
+        if self.mixtures > 1:
+            self.gw = torch.zeros(n_leaves, self.mixtures, dtype=torch.float64, device=self.device)
+            self.gw[:, 0] = 1.0
+            self.gmu = torch.zeros(n_leaves, self.mixtures, D, dtype=torch.float64, device=self.device)
+            self.gvar = torch.ones(n_leaves, self.mixtures, D, dtype=torch.float64, device=self.device)
+        lprep = []
+        for (feats, lens, G, _), kb in zip(prep, ctxs):
+            Gl = Graphs([dict(g, sid=item_leaf[np.searchsorted(codes, code(k))].astype(np.int32)) for g, k in zip(G.graphs, kb)], self.device)
+            lprep.append((feats, lens, Gl, Gl.index(n_leaves, Gl.ldg)))
+        for _ in range(self.tri_iters):
+            sums, total = None, 0.0
+            for feats, lens, G, index in lprep:
+                x = feats.to(self.device, non_blocking=True)
+                gamma, loglik = self._posteriors(x, lens, G)
+                sums = reduce(stats(gamma, x, lens, G), G, n_leaves, sums, index)
+                total += float(np.sum(loglik.cpu().numpy()))
+                del gamma
+            s = sums.cpu().numpy()
+            mu, var = m_step(s, mu, var, self.floor)
+            self._set(mu, var)
+            history.append((total + jac) / n_frames)
+        return lprep, s, mu, var, history
+
     def _fit_mixtures(self, prep, n_frames, occ0, mu, var, jac=0.0):
         """The split stages k = 1 .. M - 1 from the one-component table (mu, var) whose last pass had the occupancies occ0; `jac`
         (fmllr) is added to every pass's total log-likelihood."""
@@ -1068,6 +1425,10 @@ class Aligner:
         if self.fmllr and self.W is None:
             raise ValueError("an Aligner with fmllr has no transforms before `fit`")
         speakers = self._speakers(speakers, feats.shape[0], self.n_spk)
+        if self.triphones:
+            if self.tree is None:
+                raise ValueError("an Aligner with triphones has no tree before `fit`")
+            graphs = [self._leaf_graph(g) for g in graphs]
         lens, G = self._prepare(feats, lens, graphs)
         x = feats.to(self.device, non_blocking=True)
         if self.lda:
@@ -1107,7 +1468,8 @@ def fmllr_dim_message(dim, lda):
 
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
           batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
-          fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500):
+          fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0,
+          questions=None):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
     from . import audio as Audio
@@ -1130,6 +1492,18 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     speaker_ids = {name: i for i, name in enumerate(speakers)}
     lexicon = read_lexicon(config["path"]["lexicon_path"])
     phone_ids = phone_table(lexicon)
+    if triphones:
+        if not float(tri_min_occ) >= 1.0:
+            raise ValueError(f"tri_min_occ must be at least 1, got {tri_min_occ}")
+        if triphones < len(phone_ids) * states:
+            raise ValueError(f"triphones = {triphones} leaves is below the {len(phone_ids) * states} roots and fixed leaves")
+        real, Dt = len(phone_ids) - 3, lda if lda else 2 * n_mel           # the item table: at most R S (R + 1)^2 + 3 S rows of 1 + 2 D
+        table = (real * states * (real + 1) ** 2 + 3 * states) * (1 + 2 * Dt) * 8
+        if table > resident_bytes:
+            raise ValueError(f"the item table of {real} phones with {states} states in {Dt} dimensions may take {table} bytes, more "
+                             f"than resident_bytes = {resident_bytes}")
+        if questions is not None:
+            read_questions(questions, phone_ids)                           # refuses a bad file before any work
     stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], n_mel, sr, pp["mel"]["mel_fmin"],
                               pp["mel"]["mel_fmax"])
 
@@ -1200,7 +1574,8 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
         packed.append((feats.to(dev) if resident else feats, [frames[i] for i in batch], [items[i]["graph"] for i in batch], batch))
     aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters, lda=lda, splice=splice, lda_iters=lda_iters,
                       fmllr=fmllr, fmllr_rounds=fmllr_rounds, fmllr_iters=fmllr_iters, fmllr_sweeps=fmllr_sweeps,
-                      fmllr_min_frames=fmllr_min_frames)
+                      fmllr_min_frames=fmllr_min_frames, triphones=triphones, tri_iters=tri_iters, tri_min_occ=tri_min_occ,
+                      tri_min_gain=tri_min_gain, questions=questions, phone_ids=phone_ids if triphones else None)
     spk_of = lambda batch: [speaker_ids[items[i]["entry"][0]] for i in batch] if fmllr else None    # noqa: E731
     history = aligner.fit([p[:3] for p in packed], iters, [spk_of(p[3]) for p in packed] if fmllr else None)
 

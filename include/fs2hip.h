@@ -514,6 +514,23 @@ int fs2_align_fmllr_accum(const double* f, long ldf_b, long ldf_t, const double*
  * the device, every entry in [0, n_spk) (an utterance whose entry is not is left unwritten) */
 int fs2_align_fmllr_apply(const double* f, long ldf_b, long ldf_t, const int32_t* lens, const double* W, const int32_t* spk, int n_spk,
                           int D, double* out, long ldo_b, long ldo_t, int B, int Tmax, fs2_stream_t stream);
+/* The triphone tree (csrc/fs2_align_tree.hip; specification: the "Triphones" paragraph of fastspeech2_amd/align.py).  The item table
+ * sums [n_items][lds >= 1 + 2 D] holds {n, a[0..D), q[0..D)} per row, left / right [n_items] int32 the context symbols, member
+ * [n_sets][n_symbols] uint8 the question sets: question qi < n_sets asks whether left[item] is in set qi, question n_sets + qi
+ * whether right[item] is.  Limits, FS2_EINVAL before any launch: 1 <= n_sets <= fs2_align_max_tree_sets() (1024), min_occ >= 1.
+ * No atomics.  Nothing of this has been timed. */
+int fs2_align_max_tree_sets(void);
+/* For node m < n_nodes, the items items[offs[m] .. offs[m + 1]) of the list of n_list entries (an entry outside [0, n_items) is
+ * skipped, a symbol outside [0, n_symbols) answers no; rows of the table that are not listed are not read): per question the pooled
+ * sums of the items that answer yes and of those that answer no, both accumulated with v_mfma_f64_16x16x4_f64 (the item is the k
+ * index, ascending in steps of four), the likelihoods L = -n / 2 sum_d (log(2 pi max(q_d / n - (a_d / n)^2, floor[d])) + 1), d
+ * ascending, and gain = (L(yes) + L(no)) - L(node), -inf unless both sides have n >= min_occ.  best_q[m] = the question of the
+ * largest gain (the lowest on ties, -1 when none is eligible), best_gain[m] that gain.  gains and n_yes, each [n_nodes][ldq >=
+ * 2 n_sets] or NULL, receive the whole tables.  Every sum's order depends on the node's item count and D alone. */
+int fs2_align_tree_gains(const double* sums, long lds, int n_items, const int32_t* left, const int32_t* right, const int32_t* offs,
+                         const int32_t* items, int n_list, int n_nodes, const uint8_t* member, int n_sets, int n_symbols,
+                         const double* floor, int D, double min_occ, int32_t* best_q, double* best_gain, double* gains, double* n_yes,
+                         long ldq, fs2_stream_t stream);
 
 /* ---- objective scoring: cepstra, dynamic time warping, F0 along the path (specification: fastspeech2_amd/metrics.py) ----
  * fp64 throughout, ragged batches of pairs: pair p has alens[p] reference frames (index i) and blens[p] synthesized frames (index j),
