@@ -31,6 +31,9 @@ if __name__ == "__main__":
     parser.add_argument("--tri_min_gain", type=float, default=0.0, help="log-likelihood gain a tree split must exceed")
     parser.add_argument("--questions", type=str, default=None,
                         help="file of question sets, `name phone phone ...` per line (# is the word boundary); default: clustered from the data")
+    parser.add_argument("--transitions", type=int, default=0, choices=(0, 1),
+                        help="1: every Baum-Welch pass also trains the self-loop probability of every state and the probabilities of the "
+                             "optional silences, and decoding uses them")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -45,7 +48,7 @@ if __name__ == "__main__":
                                           fmllr=args.fmllr, fmllr_rounds=args.fmllr_rounds, fmllr_iters=args.fmllr_iters,
                                           fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames,
                                           triphones=args.triphones, tri_iters=args.tri_iters, tri_min_occ=args.tri_min_occ,
-                                          tri_min_gain=args.tri_min_gain, questions=args.questions)
+                                          tri_min_gain=args.tri_min_gain, questions=args.questions, transitions=args.transitions)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))

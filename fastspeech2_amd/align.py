@@ -17,7 +17,8 @@ the phones of word 0, optional `sp`, the phones of word 1, ..., optional `sil`. 
 choice: at hop 256 / 22050 Hz the shortest phone is then 23 ms); state j = block * S + s has emission class phone_id * S + s.
 Predecessors of state j: j (self), j - 1 (next) and, when j is the first state of block k >= 2 and block k - 1 is optional, the last
 state of block k - 2 (skip).  A path starts in state 0 or, block 0 being optional, in state S; it ends in state J - 1 or, the last
-block being optional, in state J - 1 - S.  All arcs cost 0; transitions are not trained.  Per utterance: int32 arrays `sid`, `skip`
+block being optional, in state J - 1 - S.  All arcs cost 0; transitions are not trained (with `transitions` = 1 they are: the
+"Transitions" paragraph).  Per utterance: int32 arrays `sid`, `skip`
 (-1 where there is none) and `block` of length J, and `alt` = (S, J - 1 - S).  M = the states of the mandatory blocks; an utterance
 with T < M has no path: it is reported and skipped.  J above `max_states()` (1024) is a ValueError.
 
@@ -181,6 +182,51 @@ modelling").
   sets that part a node's items alike tie bit for bit and the lower index wins.  Nothing of this has been measured against MFA,
   which cannot be run here, nothing is known about its gain on real speech, and nothing of it has been timed.
 
+Transitions (`transitions` = 1; the default 0 is everything above, unchanged: the same launches, the same numbers, the same bytes).
+Every HMM recipe (HTK, Kaldi, MFA) re-estimates, together with the Gaussians, the state transition probabilities and the
+probabilities of the optional silences; these are the arc posteriors xi of textbook Baum-Welch (Rabiner 1989).  Without them the
+choice between taking and skipping an `sp` rests on the emissions of one or two frames, and a state's expected duration carries
+no weight.  The graph topology, the emission stages and the flat start are untouched.
+  Tables (host, numpy float64, attributes of `Aligner`).  loop (n_classes,): the self-loop probability of every emission class,
+  tied exactly as the emissions are: per monophone state, per leaf after `triphones` (a leaf starts from its root's value); the
+  mixture components of a class share one value.  opt (3,): the probability that an optional block is taken; kind 0 is an optional
+  block at block index 0, kind 2 one at the last block index, kind 1 any other (`sp`).  All entries start at 0.5 (a choice); every
+  probability is clipped to [TRANS_FLOOR, 1 - TRANS_FLOOR], TRANS_FLOOR = 0.01 (Kaldi's transition floor; here a choice), so every
+  arc cost is finite.
+  Arc costs (host, `arc_costs`), per utterance w (3, J) and edge (4,), kind(k) the kind of optional block k:
+  w[0, j] = log loop[sid[j]] (self);  w[1, j], the arc j - 1 -> j, = log(1 - loop[sid[j - 1]]), plus log opt[kind(block[j])] when j is
+  the first state of an optional block (w[1, 0] = 0, unused);  w[2, j], the arc skip[j] -> j, = log(1 - loop[sid[skip[j]]]) +
+  log(1 - opt[kind(block[j] - 1)]), 0 where skip[j] < 0;  edge[0], start in state 0, = log opt[0] if block 0 is optional, else 0;
+  edge[1], start in state alt[0], = log(1 - opt[0]);  edge[2], end in state J - 1, = log(1 - loop[sid[J - 1]]);  edge[3], end in
+  state alt[1], = log(1 - loop[sid[alt[1]]]) + log(1 - opt[2]).  Leaving a state is a proper distribution: self, next, the skip
+  that starts there and the end edge where there is one sum to 1.
+  Recursions.  alpha[0, j] = edge + E[0, j] at the start states;  alpha[t, j] = E[t, j] + lse(alpha[t-1, j] + w[0, j], alpha[t-1, j-1] +
+  w[1, j], alpha[t-1, skip j] + w[2, j]);  loglik = lse over the end states e of alpha[T-1, e] + edge(e), in index order;
+  beta[T-1, e] = edge(e) at the end states, and the backward recursion adds the cost of every successor arc;  gamma as above.
+  Viterbi takes the same costs inside its max with the tie rules unchanged (the lowest backpointer code, then the lower end
+  index); backtracking is unchanged.
+  Arc posteriors.  For a in (self, next, skip):  xi[j, a] = sum over t = 1 .. T - 1 of exp(alpha[t-1, pred_a(j)] + w[a, j] + E[t, j] +
+  beta[t, j] - loglik), summed in descending t, the order in which the backward scan visits the frames (no floating-point
+  atomics).  Two further columns hold the start mass gamma[0, j] and the end mass gamma[T - 1, j], so the host never slices gamma.
+  xi[j].sum over the arcs + gamma[0, j] = sum_t gamma[t, j].
+  Update (host, `trans_step`, beside `m_step`).  With n_c the class occupancy (column 0 of the class sums; under mixtures the sum
+  over the active components, ascending) and s_c the class sum of xi[:, self]: a class with n_c >= 1 gets loop_c = clip(s_c / n_c),
+  any other keeps its value.  This is the exact maximum-likelihood estimate: a frame's mass either loops or leaves, the last
+  frame's through the end edge.  Per kind, `enter` and `skipped` are summed over the corpus: kind 1, xi[first state of the block,
+  next] and xi[first state of the block after it, skip]; kind 0, gamma[0, 0] and gamma[0, alt[0]]; kind 2, xi[J - S, next] and
+  gamma[T - 1, alt[1]].  opt_k = clip(enter / (enter + skipped)) when enter + skipped >= 1, else it is kept.  All corpus sums go
+  through `fs2_align_reduce` with host-built lists (the class list of the statistics; the list of the optional blocks, utterances
+  then blocks ascending), batch after batch in the fixed order: two runs are bit-identical.
+  Schedule.  The flat start is unchanged.  Every Baum-Welch pass of every stage (`iters`, `lda_iters`, the passes of the fMLLR
+  rounds, `tri_iters`, the mixture passes) runs under the current arc costs and updates loop and opt together with the Gaussians;
+  the statistics-only passes (LDA, fMLLR, tree) take their posteriors under the current costs and update nothing; `align`
+  decodes with the trained costs.  `fit`'s history keeps its meaning and now includes the arc terms (the fMLLR Jacobian is added
+  as before); `fit` logs one line per stage with opt and the range of 1 / (1 - loop), the expected frames per state.  With every
+  entry at 0.5 every path of an utterance carries the same arc total, (T + the number of its optional blocks) log 0.5, so the
+  posteriors of the first pass equal the default run's: that is why 0.5 is a harmless start.
+  Quality against MFA unmeasured (it cannot be run here); transition probabilities are known to matter less than emissions, the
+  silence probabilities more; what either changes on real speech is unknown, and no timing measured yet.
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
 update runs on the host in numpy.  Every sum's order is a function of the batch shape (for the speaker statistics: and of the
@@ -198,6 +244,7 @@ from . import _lib, ops, ragged
 
 SIL, SP, SPN = "sil", "sp", "spn"
 VAR_FLOOR = 1e-2
+TRANS_FLOOR = 0.01
 _SPLIT = re.compile(r"[,;.\-\?\!\s+]")
 
 
@@ -303,6 +350,53 @@ def split_classes(w, mu, var, ncomp, occ, k, min_split_occ=40.0, step=0.2):
     return w, mu, var, ncomp
 
 
+def block_kinds(graph):
+    """The kind of every block: -1 mandatory, 0 optional at block index 0, 2 optional at the last block index, 1 any other optional
+    block (`sp`)."""
+    blocks = graph["blocks"]
+    return np.array([-1 if not b[2] else 0 if k == 0 else 2 if k == len(blocks) - 1 else 1 for k, b in enumerate(blocks)], np.int64)
+
+
+def _block_starts(graph):
+    """The first state of every block, in block order."""
+    block = np.asarray(graph["block"])
+    return np.nonzero(np.concatenate([[True], block[1:] != block[:-1]]))[0]
+
+
+def arc_costs(graph, loop, opt):
+    """The arc costs of the module docstring for one graph from the tables loop (n_classes,) and opt (3,) -> (w (3, J): self, next,
+    skip into state j; edge (4,): start in state 0, start in alt[0], end in state J - 1, end in alt[1]), float64 log-probabilities."""
+    sid, skip, block = (np.asarray(graph[k], np.int64) for k in ("sid", "skip", "block"))
+    loop, opt = np.asarray(loop, np.float64), np.asarray(opt, np.float64)
+    J, kind, alt = len(sid), block_kinds(graph), graph["alt"]
+    stay, leave, take, pass_ = np.log(loop[sid]), np.log(1.0 - loop[sid]), np.log(opt), np.log(1.0 - opt)
+    w = np.zeros((3, J))
+    w[0] = stay
+    w[1, 1:] = leave[:-1]
+    first = np.zeros(J, bool)
+    first[_block_starts(graph)] = True
+    enter = first & (kind[block] >= 0)
+    enter[0] = False                                                       # block 0 is entered by the start edge
+    w[1, enter] += take[kind[block[enter]]]
+    has = skip >= 0
+    w[2, has] = leave[skip[has]] + pass_[kind[block[has] - 1]]
+    edge = np.array([take[0] if kind[0] == 0 else 0.0, pass_[0], leave[J - 1], leave[alt[1]] + pass_[2] if alt[1] >= 0 else 0.0])
+    return w, edge
+
+
+def trans_step(n, s, enter, skipped, loop, opt):
+    """The transition update of the module docstring: n, s (C,) the class occupancies and the class sums of xi[:, self]; enter, skipped
+    (3,) the masses per kind of optional block -> (loop, opt).  A class with n < 1 and a kind with enter + skipped < 1 keep their
+    values; every estimate is clipped to [TRANS_FLOOR, 1 - TRANS_FLOOR]."""
+    n, s, enter, skipped = (np.asarray(v, np.float64) for v in (n, s, enter, skipped))
+    ok = n >= 1.0
+    new_loop = np.where(ok, np.clip(s / np.where(ok, n, 1.0), TRANS_FLOOR, 1.0 - TRANS_FLOOR), loop)
+    tot = enter + skipped
+    ok = tot >= 1.0
+    new_opt = np.where(ok, np.clip(enter / np.where(ok, tot, 1.0), TRANS_FLOOR, 1.0 - TRANS_FLOOR), opt)
+    return new_loop, new_opt
+
+
 # ------------------------------------------------------------------------------------------------ TextGrid
 def write_textgrid(path, words, phones, xmax):
     """Long Praat text format, IntervalTiers `words` and `phones` of (start, end, text) intervals; times are written with repr, so
@@ -373,6 +467,39 @@ class Graphs:
         self.alt = torch.tensor([g["alt"] for g in graphs], dtype=torch.int32, device=device).reshape(-1, 2)
         self.jlens = torch.tensor(self.jl, dtype=torch.int32, device=device)
         self.ldg = max(self.Jmax, 1)
+        self.w, self.edge, self._arc_index = None, None, {}
+
+    def set_arcs(self, loop, opt):
+        """The padded device copies w (B, 3, ldg) and edge (B, 4) of every graph's `arc_costs` (0 in the padding); rebuilt after each
+        update of the tables."""
+        w, edge = np.zeros((len(self.graphs), 3, self.ldg)), np.zeros((len(self.graphs), 4))
+        for b, g in enumerate(self.graphs):
+            w[b, :, :self.jl[b]], edge[b] = arc_costs(g, loop, opt)
+        dev = self.sid.device
+        self.w, self.edge = torch.from_numpy(w).to(dev), torch.from_numpy(edge).to(dev)
+
+    def arc_index(self, n_classes):
+        """The two CSR lists that reduce the arc posteriors xi (B, ldg, 5): the class list of `index` and the list of the optional
+        blocks, row classes (kind 0 enter, skipped, kind 1 enter, skipped, kind 2 enter, skipped) as the module docstring names the
+        states, utterances then blocks ascending.  Cached per number of classes."""
+        if n_classes not in self._arc_index:
+            rows = [[] for _ in range(6)]
+            for b, g in enumerate(self.graphs):
+                first, at = _block_starts(g), b * self.ldg
+                for k, kind in enumerate(block_kinds(g)):
+                    if kind == 0:
+                        rows[0].append(at), rows[1].append(at + g["alt"][0])
+                    elif kind == 1:
+                        rows[2].append(at + first[k]), rows[3].append(at + first[k + 1])
+                    elif kind == 2:
+                        rows[4].append(at + first[k]), rows[5].append(at + g["alt"][1])
+            offs = np.zeros(7, np.int64)
+            np.cumsum([len(r) for r in rows], out=offs[1:])
+            items = np.array([i for r in rows for i in r] or [0], np.int64)    # never an empty tensor: the lists bound what is read
+            dev = self.sid.device
+            self._arc_index[n_classes] = (self.index(n_classes, self.ldg),
+                                          (torch.from_numpy(offs.astype(np.int32)).to(dev), torch.from_numpy(items.astype(np.int32)).to(dev)))
+        return self._arc_index[n_classes]
 
     def index(self, n_classes, ld_j, mixtures=1):
         """CSR (class -> rows b * ld_j + j of the partials), utterances then states ascending: (offs, items) on the device.  With
@@ -498,6 +625,50 @@ def backward(E, lens, G, alpha, loglik, out=None):
               G.ldg, G.alt.data_ptr(), alpha.data_ptr(), alpha.stride(0), alpha.stride(1), loglik.data_ptr(), gamma.data_ptr(),
               gamma.stride(0), gamma.stride(1), B, Tmax, G.Jmax, ops._stream())
     return gamma
+
+
+def _check_arcs(w, edge, B, G):
+    _no_host(w=w, edge=edge)
+    w, edge = _dev(w, torch.float64, "w"), _dev(edge, torch.float64, "edge", 2)
+    if w.shape[0] != B or w.shape[1] != 3 or w.shape[2] < G.Jmax or (B and w.stride(0) != 3 * w.stride(1)) or \
+            tuple(edge.shape) != (B, 4) or not edge.is_contiguous():
+        raise ValueError(f"w {tuple(w.shape)} (strides {w.stride()}) and edge {tuple(edge.shape)} are not the arc costs [B][3][ldw] and "
+                         f"[B][4] of {B} utterances of up to {G.Jmax} states")
+    return w, edge
+
+
+def forward_arcs(E, lens, G, w, edge, out=None):
+    """`forward` under the arc costs w (B, 3, >= Jmax) and edge (B, 4) -> (alpha like E, loglik (B,)) on the device."""
+    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
+    w, edge = _check_arcs(w, edge, B, G)
+    alpha = torch.empty_like(E) if out is None else _dev(out, torch.float64, "out")
+    if alpha.shape != E.shape:
+        raise ValueError("out must have E's shape")
+    loglik = torch.empty(B, dtype=torch.float64, device=E.device)
+    _lib.call("fs2_align_forward_arcs", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), w.data_ptr(), w.stride(1), edge.data_ptr(), alpha.data_ptr(), alpha.stride(0),
+              alpha.stride(1), loglik.data_ptr(), B, Tmax, G.Jmax, ops._stream())
+    return alpha, loglik
+
+
+def backward_arcs(E, lens, G, w, edge, alpha, loglik, out=None, xi=None):
+    """`backward` under the arc costs -> (gamma, written over alpha unless `out` is given; xi (B, >= Jmax, 5): the arc posteriors
+    self, next, skip of every state, then its start mass gamma[0, j] and its end mass gamma[T - 1, j])."""
+    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
+    w, edge = _check_arcs(w, edge, B, G)
+    alpha = _dev(alpha, torch.float64, "alpha")
+    gamma = alpha if out is None else _dev(out, torch.float64, "out")
+    loglik = _dev(loglik, torch.float64, "loglik", 1)
+    if alpha.shape != E.shape or gamma.shape != E.shape or loglik.shape[0] != B:
+        raise ValueError("alpha and out must have E's shape, loglik B values")
+    xi = torch.empty(B, G.ldg, 5, dtype=torch.float64, device=E.device) if xi is None else _dev(xi, torch.float64, "xi")
+    if xi.shape[0] != B or xi.shape[1] < G.Jmax or xi.shape[2] != 5:
+        raise ValueError(f"xi {tuple(xi.shape)} is not ({B}, >= {G.Jmax}, 5)")
+    _lib.call("fs2_align_backward_arcs", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), w.data_ptr(), w.stride(1), edge.data_ptr(), alpha.data_ptr(), alpha.stride(0),
+              alpha.stride(1), loglik.data_ptr(), gamma.data_ptr(), gamma.stride(0), gamma.stride(1), xi.data_ptr(), xi.stride(0),
+              xi.stride(1), B, Tmax, G.Jmax, ops._stream())
+    return gamma, xi
 
 
 def stats(gamma, x, lens, G, out=None):
@@ -1011,6 +1182,21 @@ def viterbi(E, lens, G, out=None):
     return bp, end, score
 
 
+def viterbi_arcs(E, lens, G, w, edge, out=None):
+    """`viterbi` under the arc costs; the score includes the end edge."""
+    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
+    w, edge = _check_arcs(w, edge, B, G)
+    bp = torch.empty(E.shape, dtype=torch.uint8, device=E.device) if out is None else _dev(out, torch.uint8, "out")
+    if bp.shape != E.shape:
+        raise ValueError("out must have E's shape")
+    end = torch.empty(B, dtype=torch.int32, device=E.device)
+    score = torch.empty(B, dtype=torch.float64, device=E.device)
+    _lib.call("fs2_align_viterbi_arcs", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), w.data_ptr(), w.stride(1), edge.data_ptr(), bp.data_ptr(), bp.stride(0),
+              bp.stride(1), end.data_ptr(), score.data_ptr(), B, Tmax, G.Jmax, ops._stream())
+    return bp, end, score
+
+
 def backtrack(bp, lens, G, end):
     """-> frames per block (B, nbmax) int32 on the device."""
     bp = _dev(bp, torch.uint8, "bp")
@@ -1035,11 +1221,13 @@ class Aligner:
     `fmllr` = 1 `fit` goes on to the speaker transforms W (n_spk, D, D + 1) and to tables trained on the adapted features, and
     `fit` and `align` take the speaker index of every utterance.  With `triphones` = L > 0 (and `phone_ids`, the phone table) `fit`
     goes on from the last single-Gaussian table to the decision tree `tree` (arrays over its nodes) and to tables over its leaves,
-    `n_classes` becomes the leaf count and `align` decodes on the leaves."""
+    `n_classes` becomes the leaf count and `align` decodes on the leaves.  With `transitions` = 1 every Baum-Welch pass also trains
+    loop (n_classes,) and opt (3,) (numpy float64: the self-loop probability of every class, the probability that an optional block
+    of kind 0 / 1 / 2 is taken), every pass runs under their arc costs and `align` decodes with them."""
 
     def __init__(self, n_classes, dim, states=2, device="cuda", mixtures=1, mix_iters=4, min_split_occ=40, lda=0, splice=3, lda_iters=4,
                  fmllr=0, fmllr_rounds=2, fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100,
-                 tri_min_gain=0.0, questions=None, phone_ids=None):
+                 tri_min_gain=0.0, questions=None, phone_ids=None, transitions=0):
         self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
         if n_classes % states:
             raise ValueError(f"n_classes {n_classes} is not a multiple of states {states}")
@@ -1047,6 +1235,10 @@ class Aligner:
         self.mu = torch.zeros(n_classes, dim, dtype=torch.float64, device=self.device)
         self.var = torch.ones(n_classes, dim, dtype=torch.float64, device=self.device)
         self.floor = np.zeros(dim)
+        self.transitions = int(transitions)
+        if self.transitions not in (0, 1):
+            raise ValueError(f"transitions must be 0 or 1, got {transitions}")
+        self.loop, self.opt = np.full(n_classes, 0.5), np.full(3, 0.5)
         self.mixtures, self.mix_iters, self.min_split_occ = int(mixtures), int(mix_iters), float(min_split_occ)
         self.lda, self.splice, self.lda_iters, self.P, self.o = int(lda), int(splice), int(lda_iters), None, None
         if self.lda != 0:
@@ -1121,6 +1313,43 @@ class Aligner:
             raise ValueError("an Aligner with fmllr needs the speaker index of every utterance (`speakers`)")
         return _speaker_list(speakers, B, n_spk if n_spk is not None else np.iinfo(np.int32).max)
 
+    def _arcs(self, prep):
+        """The device arc costs of every batch, rebuilt from the tables (nothing without transitions)."""
+        if self.transitions:
+            for _, _, G, _ in prep:
+                G.set_arcs(self.loop, self.opt)
+
+    def _tacc(self):
+        """The accumulators of one pass's arc posteriors: [class sums (C, 5), sums per kind of optional block (6, 5)]."""
+        return [None, None] if self.transitions else None
+
+    def _fb(self, E, lens, G, tacc=None):
+        """gamma and the log-likelihoods of one batch from its emissions: forward and backward, with transitions under the current
+        arc costs, the sums of the arc posteriors added to `tacc`."""
+        if not self.transitions:
+            alpha, loglik = forward(E, lens, G)
+            return backward(E, lens, G, alpha, loglik), loglik
+        alpha, loglik = forward_arcs(E, lens, G, G.w, G.edge)
+        gamma, xi = backward_arcs(E, lens, G, G.w, G.edge, alpha, loglik)
+        if tacc is not None:
+            classes, kinds = G.arc_index(self.n_classes)
+            tacc[0] = reduce(xi, G, self.n_classes, tacc[0], classes)
+            tacc[1] = reduce(xi, G, 6, tacc[1], kinds)
+        return gamma, loglik
+
+    def _trans_step(self, n, tacc, prep):
+        """The transition update after a pass with the class occupancies n, and the new arc costs on every batch of `prep`."""
+        if not self.transitions:
+            return
+        c, o = tacc[0].cpu().numpy(), tacc[1].cpu().numpy()
+        self.loop, self.opt = trans_step(n, c[:, 0], o[[0, 2, 4], [3, 1, 1]], o[[1, 3, 5], [3, 2, 4]], self.loop, self.opt)
+        self._arcs(prep)
+
+    def _trans_log(self, stage):
+        if self.transitions:
+            d = 1.0 / (1.0 - self.loop)
+            print(f"transitions: {stage}, opt " + " ".join(f"{v:.4f}" for v in self.opt) + f", frames per state {d.min():.4g} .. {d.max():.4g}")
+
     def fit(self, batches, iters=12, speakers=None):
         """batches: [(feats (B, Tmax, D) float64 on the device or the host, lens, graphs)].  Flat start, then `iters` Baum-Welch
         passes (then, with lda, fmllr and mixtures, their stages); returns the log-likelihood per frame of every pass.  `speakers`
@@ -1137,6 +1366,8 @@ class Aligner:
             prep.append((feats, lens, G, G.index(self.n_classes, G.ldg)))
         n_frames = sum(sum(lens) for _, lens, _, _ in prep)
         cols = 1 + 2 * self.dim
+        self.loop, self.opt = np.full(self.n_classes, 0.5), np.full(3, 0.5)
+        self._arcs(prep)
 
         # flat start: the hard assignment as a one-hot gamma through the same statistics kernels
         sums = None
@@ -1162,19 +1393,20 @@ class Aligner:
 
         history = []
         for _ in range(iters):
-            sums, total = None, 0.0
+            sums, total, tacc = None, 0.0, self._tacc()
             for feats, lens, G, index in prep:
                 x = feats.to(self.device, non_blocking=True)
                 E = emit(x, lens, G, self.mu, self.var)
-                alpha, loglik = forward(E, lens, G)
-                gamma = backward(E, lens, G, alpha, loglik)
+                gamma, loglik = self._fb(E, lens, G, tacc)
                 sums = reduce(stats(gamma, x, lens, G), G, self.n_classes, sums, index)
                 total += float(np.sum(loglik.cpu().numpy()))
-                del E, alpha, gamma
+                del E, gamma
             s = sums.cpu().numpy()
             mu, var = m_step(s, mu, var, self.floor)
             self._set(mu, var)
+            self._trans_step(s[:, 0], tacc, prep)
             history.append(total / n_frames)
+        self._trans_log("monophones")
         if self.lda:
             prep, s, mu, var, more = self._fit_lda(prep, n_frames)
             history += more
@@ -1189,11 +1421,9 @@ class Aligner:
             history += self._fit_mixtures(prep, n_frames, s[:, 0], mu, var, jac)
         return history
 
-    def _posteriors(self, x, lens, G):
-        """gamma and the log-likelihoods of one batch under the single-Gaussian table."""
-        E = emit(x, lens, G, self.mu, self.var)
-        alpha, loglik = forward(E, lens, G)
-        return backward(E, lens, G, alpha, loglik), loglik
+    def _posteriors(self, x, lens, G, tacc=None):
+        """gamma and the log-likelihoods of one batch under the single-Gaussian table (and, with transitions, the arc costs)."""
+        return self._fb(emit(x, lens, G, self.mu, self.var), lens, G, tacc)
 
     def _project(self, x, lens):
         return project(splice(x, lens, self.n_mel, self.splice), lens, self.P, self.o)
@@ -1234,17 +1464,19 @@ class Aligner:
         mu, var = m_step(s, np.tile(g_mean, (C, 1)), np.tile(g_var, (C, 1)), self.floor)
         self._set(mu, var)
         for _ in range(self.lda_iters):
-            sums, total = None, 0.0
+            sums, total, tacc = None, 0.0, self._tacc()
             for zf, lens, G, index in zprep:
                 z = zf.to(self.device, non_blocking=True)
-                gamma, loglik = self._posteriors(z, lens, G)
+                gamma, loglik = self._posteriors(z, lens, G, tacc)
                 sums = reduce(stats(gamma, z, lens, G), G, C, sums, index)
                 total += float(np.sum(loglik.cpu().numpy()))
                 del gamma
             s = sums.cpu().numpy()
             mu, var = m_step(s, mu, var, self.floor)
             self._set(mu, var)
+            self._trans_step(s[:, 0], tacc, zprep)
             history.append(total / n_frames)
+        self._trans_log("lda")
         return zprep, s, mu, var, history
 
     def _fit_fmllr(self, prep, speakers, n_frames, s, mu, var):
@@ -1280,17 +1512,19 @@ class Aligner:
             self.W.copy_(torch.from_numpy(np.ascontiguousarray(W)))
             hprep = adapted()
             for _ in range(self.fmllr_iters):
-                sums, total = None, 0.0
+                sums, total, tacc = None, 0.0, self._tacc()
                 for fh, lens, G, index in hprep:
                     x = fh.to(self.device, non_blocking=True)
-                    gamma, loglik = self._posteriors(x, lens, G)
+                    gamma, loglik = self._posteriors(x, lens, G, tacc)
                     sums = reduce(stats(gamma, x, lens, G), G, C, sums, index)
                     total += float(np.sum(loglik.cpu().numpy()))
                     del gamma
                 s = sums.cpu().numpy()
                 mu, var = m_step(s, mu, var, self.floor)
                 self._set(mu, var)
+                self._trans_step(s[:, 0], tacc, hprep)
                 history.append((total + jac) / n_frames)
+        self._trans_log("fmllr")
         return hprep, s, mu, var, history, jac
 
     def _leaf_graph(self, graph):
@@ -1360,6 +1594,7 @@ class Aligner:
         del sums
         self.n_classes = n_leaves
         self._set(mu, var)
+        self.loop = self.loop[leaf_root]                                   # a leaf starts from its root's self-loop probability
         if self.mixtures > 1:
             self.gw = torch.zeros(n_leaves, self.mixtures, dtype=torch.float64, device=self.device)
             self.gw[:, 0] = 1.0
@@ -1369,18 +1604,21 @@ class Aligner:
         for (feats, lens, G, _), kb in zip(prep, ctxs):
             Gl = Graphs([dict(g, sid=item_leaf[np.searchsorted(codes, code(k))].astype(np.int32)) for g, k in zip(G.graphs, kb)], self.device)
             lprep.append((feats, lens, Gl, Gl.index(n_leaves, Gl.ldg)))
+        self._arcs(lprep)
         for _ in range(self.tri_iters):
-            sums, total = None, 0.0
+            sums, total, tacc = None, 0.0, self._tacc()
             for feats, lens, G, index in lprep:
                 x = feats.to(self.device, non_blocking=True)
-                gamma, loglik = self._posteriors(x, lens, G)
+                gamma, loglik = self._posteriors(x, lens, G, tacc)
                 sums = reduce(stats(gamma, x, lens, G), G, n_leaves, sums, index)
                 total += float(np.sum(loglik.cpu().numpy()))
                 del gamma
             s = sums.cpu().numpy()
             mu, var = m_step(s, mu, var, self.floor)
             self._set(mu, var)
+            self._trans_step(s[:, 0], tacc, lprep)
             history.append((total + jac) / n_frames)
+        self._trans_log("triphones")
         return lprep, s, mu, var, history
 
     def _fit_mixtures(self, prep, n_frames, occ0, mu, var, jac=0.0):
@@ -1400,20 +1638,25 @@ class Aligner:
             for _ in range(self.mix_iters):
                 for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
                     dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
-                sums, total = None, 0.0
+                sums, total, tacc = None, 0.0, self._tacc()
                 for (feats, lens, G, _), idx in zip(prep, index):
                     x = feats.to(self.device, non_blocking=True)
                     resp = torch.empty(x.shape[0], x.shape[1], G.ldg, M, dtype=torch.float64, device=self.device)
                     E = emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar, resp=resp)
-                    alpha, loglik = forward(E, lens, G)
-                    gamma = backward(E, lens, G, alpha, loglik)
+                    gamma, loglik = self._fb(E, lens, G, tacc)
                     sums = reduce(stats_gmm(gamma, resp, x, lens, G), G, C, sums, idx)
                     total += float(np.sum(loglik.cpu().numpy()))
-                    del E, alpha, gamma, resp
+                    del E, gamma, resp
                 s = sums.cpu().numpy().reshape(C, M, 1 + 2 * D)
                 occ = s[:, :, 0]
                 w, gmu, gvar = m_step_gmm(s, w, gmu, gvar, ncomp, self.floor)
+                if self.transitions:
+                    n_c = np.zeros(C)
+                    for m in range(M):                                     # the class occupancy: the active components, ascending
+                        n_c = n_c + np.where(m < ncomp, occ[:, m], 0.0)
+                    self._trans_step(n_c, tacc, prep)
                 history.append((total + jac) / n_frames)
+            self._trans_log(f"mixtures stage {k + 1}")
         for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
             dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
         self.ncomp = ncomp
@@ -1438,18 +1681,23 @@ class Aligner:
         if self.fmllr:
             x = fmllr_apply(x, lens, self.W, speakers)
         E = emit(x, lens, G, self.mu, self.var) if self.mixtures == 1 else emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar)
-        bp, end, _ = viterbi(E, lens, G)
+        if self.transitions:
+            G.set_arcs(self.loop, self.opt)
+            bp, end, _ = viterbi_arcs(E, lens, G, G.w, G.edge)
+        else:
+            bp, end, _ = viterbi(E, lens, G)
         frames = backtrack(bp, lens, G, end).cpu().numpy()
         return [frames[b, :len(g["blocks"])].copy() for b, g in enumerate(graphs)]
 
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
-def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmllr_dim=0):
+def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmllr_dim=0, transitions=0):
     """`ragged.greedy_batches` of (frames, states) under `budget` bytes of device buffers: E, alpha / gamma and backpointers (17 B per
     cell), features, partials; with `mixtures` = M > 1 also the responsibilities (8 M B per cell) and M times the partials; with
     `splice_dim` = D_s > 0 (LDA) also the spliced frames, D_s doubles per frame, and their partials while the statistics are taken
     (the scatter workspace, at most 82 MB for any batch, is not counted); with `fmllr_dim` = D > 0 also the frame weights c, h and
-    the adapted frames, 3 D doubles per frame (the accumulation workspace, at most 141 MB and 16 B per utterance, is not counted)."""
+    the adapted frames, 3 D doubles per frame (the accumulation workspace, at most 141 MB and 16 B per utterance, is not counted);
+    with `transitions` also the arc costs w and the second partial table xi, 3 + 5 doubles per state."""
     if mixtures == 1:
         base = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
     else:
@@ -1458,6 +1706,9 @@ def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmll
     if fmllr_dim:
         lda_cost = cost
         cost = lambda n, T, J: lda_cost(n, T, J) + n * T * 3 * fmllr_dim * 8               # noqa: E731
+    if transitions:
+        plain_cost = cost
+        cost = lambda n, T, J: plain_cost(n, T, J) + n * J * (3 + 5) * 8                  # noqa: E731
     return ragged.greedy_batches(list(zip(frames, states)), budget, cost)
 
 
@@ -1469,7 +1720,7 @@ def fmllr_dim_message(dim, lda):
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
           batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
           fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0,
-          questions=None):
+          questions=None, transitions=0):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
     from . import audio as Audio
@@ -1477,6 +1728,8 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
     if not 1 <= mixtures <= max_mixtures():
         raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
+    if transitions not in (0, 1):
+        raise ValueError(f"transitions must be 0 or 1, got {transitions}")
     raw, out_dir = config["path"]["raw_path"], os.path.join(config["path"]["preprocessed_path"], "TextGrid")
     pp = config["preprocessing"]
     sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
@@ -1566,7 +1819,7 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     frames, nstates = [it["x"].shape[0] for it in items], [len(it["graph"]["sid"]) for it in items]
     resident = sum(frames) * D * 8 <= resident_bytes
     packed = []
-    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures, Ds, Df):
+    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures, Ds, Df, transitions):
         feats = torch.zeros(len(batch), max(frames[i] for i in batch), D, dtype=torch.float64)
         for r, i in enumerate(batch):
             feats[r, :frames[i]] = items[i]["x"]
@@ -1575,7 +1828,8 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters, lda=lda, splice=splice, lda_iters=lda_iters,
                       fmllr=fmllr, fmllr_rounds=fmllr_rounds, fmllr_iters=fmllr_iters, fmllr_sweeps=fmllr_sweeps,
                       fmllr_min_frames=fmllr_min_frames, triphones=triphones, tri_iters=tri_iters, tri_min_occ=tri_min_occ,
-                      tri_min_gain=tri_min_gain, questions=questions, phone_ids=phone_ids if triphones else None)
+                      tri_min_gain=tri_min_gain, questions=questions, phone_ids=phone_ids if triphones else None,
+                      transitions=transitions)
     spk_of = lambda batch: [speaker_ids[items[i]["entry"][0]] for i in batch] if fmllr else None    # noqa: E731
     history = aligner.fit([p[:3] for p in packed], iters, [spk_of(p[3]) for p in packed] if fmllr else None)
 

@@ -14,6 +14,8 @@
 //   fs2_align_forward    the three scans: one workgroup per utterance, one state per lane, the previous frame's row in LDS,
 //   fs2_align_backward   double-buffered, so a frame costs one barrier; E / alpha / gamma rows are read and written as
 //   fs2_align_viterbi    consecutive f64 (bytes for the backpointers), the next frame's operands are loaded one frame ahead
+//   fs2_align_*_arcs     the same three scans with a cost on every arc and edge; the backward scan also sums the arc posteriors
+//   fs2_align_*_arcs     the same three scans with a cost on every arc and edge; the backward scan also sums the arc posteriors
 //   fs2_align_stats      P[b][j] = sum_t gamma[t][j] [1, x_t, x_t^2]: gamma^T [1 x x^2] per utterance, 32 x 32 tiles of (j, d), frames
 //                        staged in LDS 32 at a time, summed in ascending t
 //   fs2_align_stats_gmm  the same over rows (j, m) with g = gamma[t][j] r[t][j][m], multiplied while a frame block is staged
@@ -297,10 +299,14 @@ extern "C" int fs2_align_emit_gmm(const double* x, long ldx_b, long ldx_t, const
 // Lane j owns state j.  prev[j + 1] holds the previous frame's value of state j and prev[0] = -inf, so the "next" arc of state 0
 // needs no branch; the skip predecessor is one more LDS read.  Frame t reads buffer (t - 1) & 1 and writes buffer t & 1; the barrier
 // at the top of frame t + 1 orders those writes before their readers and frame t's reads before frame t + 1's overwrites.
-template <int NT>
+// ARCS (the *_arcs entry points): lane j keeps the costs w[0..2][j] of its three incoming arcs in registers and adds each to the
+// predecessor's value before the lse (the max); the start states take edge[0] / edge[1], the end states edge[2] / edge[3].  Without
+// ARCS none of that is compiled: the code, and with it every bit, is what it was before the costs existed.
+template <int NT, bool ARCS>
 __global__ void __launch_bounds__(NT) align_forward_kernel(const double* __restrict__ E, long lde_b, long lde_t,
                                                            const int32_t* __restrict__ lens, const int32_t* __restrict__ jlens,
                                                            const int32_t* __restrict__ skip, long ldg, const int32_t* __restrict__ alt,
+                                                           const double* __restrict__ w, long ldw, const double* __restrict__ edge,
                                                            double* __restrict__ alpha, long lda_b, long lda_t,
                                                            double* __restrict__ loglik, int Tmax, int Jmax) {
     __shared__ double row[2][NT + 1];
@@ -315,9 +321,21 @@ __global__ void __launch_bounds__(NT) align_forward_kernel(const double* __restr
     if (sk < 0 || sk >= J) sk = -1;
     const double* Eb = E + (size_t)b * lde_b + j;
     double* Ab = alpha + (size_t)b * lda_b + j;
+    double w0 = 0.0, w1 = 0.0, w2 = 0.0;
+    if constexpr (ARCS) {
+        if (on) {
+            const double* Wb = w + (size_t)b * 3 * ldw + j;
+            w0 = Wb[0];
+            w1 = Wb[ldw];
+            w2 = Wb[2 * ldw];
+        }
+    }
     if (j == 0) row[0][0] = row[1][0] = al_ninf();
     double a = al_ninf();
-    if (on && (j == 0 || j == s_alt)) a = Eb[0];
+    if (on && (j == 0 || j == s_alt)) {
+        if constexpr (ARCS) a = edge[4 * b + (j == 0 ? 0 : 1)] + Eb[0];
+        else a = Eb[0];
+    }
     if (on) Ab[0] = a;
     row[0][j + 1] = a;
     double e_next = (on && T > 1) ? Eb[lde_t] : 0.0;
@@ -327,7 +345,8 @@ __global__ void __launch_bounds__(NT) align_forward_kernel(const double* __restr
         if (on && t + 1 < T) e_next = Eb[(size_t)(t + 1) * lde_t];
         const double* p = row[(t - 1) & 1];
         if (on) {
-            a = e + al_lse3(p[j + 1], p[j], sk >= 0 ? p[sk + 1] : al_ninf());
+            if constexpr (ARCS) a = e + al_lse3(p[j + 1] + w0, p[j] + w1, sk >= 0 ? p[sk + 1] + w2 : al_ninf());
+            else a = e + al_lse3(p[j + 1], p[j], sk >= 0 ? p[sk + 1] : al_ninf());
             Ab[(size_t)t * lda_t] = a;
         }
         row[t & 1][j + 1] = a;
@@ -335,21 +354,38 @@ __global__ void __launch_bounds__(NT) align_forward_kernel(const double* __restr
     __syncthreads();
     if (j == 0) {
         const double* p = row[(T - 1) & 1];
-        const double last = p[J];
-        loglik[b] = (e_alt >= 0 && e_alt < J - 1) ? al_lse2(p[e_alt + 1], last) : last;
+        if constexpr (ARCS) {
+            const double last = p[J] + edge[4 * b + 2];
+            loglik[b] = (e_alt >= 0 && e_alt < J - 1) ? al_lse2(p[e_alt + 1] + edge[4 * b + 3], last) : last;
+        } else {
+            const double last = p[J];
+            loglik[b] = (e_alt >= 0 && e_alt < J - 1) ? al_lse2(p[e_alt + 1], last) : last;
+        }
     }
 }
 
 // beta never leaves the chip: buffer row t holds E[t][k] + beta[t][k], what the predecessors of k add up.  Successors of state j
 // are j, j + 1 and the one state whose skip predecessor is j (to[j], built in LDS from skip).  gamma may be written over alpha.
-template <int NT>
+// ARCS: the successor arcs carry their costs (lane j keeps w[0][j], w[1][j + 1] and w[2][to[j]] for them) and beta[T - 1] is the end
+// edge.  The arc posteriors xi[j][a] = sum_t exp(alpha[t - 1][pred_a(j)] + w[a][j] + E[t][j] + beta[t][j] - loglik) need the
+// predecessors' alpha[t - 1]: in frame t every lane publishes the alpha[t][j] it prefetched a frame earlier in arow[t & 1][j + 1]
+// (arow[.][0] = -inf, the "next" arc of state 0), beside row[t & 1][j], and in frame t - 1, after that frame's barrier, lane j adds
+// the three terms of the transition into frame t + 1 from arow[t & 1] and from its own E + beta of frame t + 1, kept in a register
+// (two frames back).  arow follows row's argument: frame t writes buffer t & 1 and reads buffer (t + 1) & 1, the barrier at the top of
+// frame t orders frame t + 1's writes before these reads, the barrier at the top of frame t - 1 orders these reads before frame
+// t - 1's overwrites of buffer (t + 1) & 1.  The last transition, into frame 1, is added after one more barrier behind the loop.  So
+// xi is summed in descending t.  alpha[t][.] is read from memory by its own lane only, a frame before that lane writes gamma[t][.]:
+// gamma over alpha stays legal.  Columns 3 and 4 of xi are gamma[0][j] and gamma[T - 1][j].
+template <int NT, bool ARCS>
 __global__ void __launch_bounds__(NT) align_backward_kernel(const double* __restrict__ E, long lde_b, long lde_t,
                                                             const int32_t* __restrict__ lens, const int32_t* __restrict__ jlens,
                                                             const int32_t* __restrict__ skip, long ldg, const int32_t* __restrict__ alt,
+                                                            const double* __restrict__ w, long ldw, const double* __restrict__ edge,
                                                             const double* alpha, long lda_b, long lda_t,
                                                             const double* __restrict__ loglik, double* gamma, long ldo_b, long ldo_t,
-                                                            int Tmax, int Jmax) {
+                                                            double* __restrict__ xi, long ldx_b, long ldx_j, int Tmax, int Jmax) {
     __shared__ double row[2][NT + 1];
+    __shared__ double arow[ARCS ? 2 : 1][ARCS ? NT + 1 : 1];
     __shared__ int to[NT];
     const int b = blockIdx.x, j = threadIdx.x, T = al_len(lens, b, Tmax), J = al_len(jlens, b, min(Jmax, NT));
     if (T == 0 || J == 0) return;
@@ -361,6 +397,9 @@ __global__ void __launch_bounds__(NT) align_backward_kernel(const double* __rest
     to[j] = -1;
     row[0][j] = row[1][j] = al_ninf();                                     // states >= J stay -inf: the "next" arc of state J - 1
     if (j == 0) row[0][NT] = row[1][NT] = al_ninf();
+    if constexpr (ARCS) {
+        if (j == 0) arow[0][0] = arow[1][0] = al_ninf();
+    }
     __syncthreads();
     if (sk >= 0) to[sk] = j;                                               // at most one state skips from sk
     __syncthreads();
@@ -368,11 +407,31 @@ __global__ void __launch_bounds__(NT) align_backward_kernel(const double* __rest
     const double* Eb = E + (size_t)b * lde_b + j;
     const double* Ab = alpha + (size_t)b * lda_b + j;
     double* Gb = gamma + (size_t)b * ldo_b + j;
+    double w0 = 0.0, w1 = 0.0, w2 = 0.0, w1n = 0.0, w2s = 0.0;           // incoming self / next / skip, outgoing next / skip
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0, x4 = 0.0, eb1 = al_ninf(), eb2 = al_ninf();
     double beta = (on && (j == J - 1 || j == e_alt)) ? 0.0 : al_ninf();
+    if constexpr (ARCS) {
+        if (on) {
+            const double* Wb = w + (size_t)b * 3 * ldw;
+            w0 = Wb[j];
+            w1 = Wb[ldw + j];
+            w2 = Wb[2 * ldw + j];
+            if (j + 1 < J) w1n = Wb[ldw + j + 1];
+            if (st >= 0) w2s = Wb[2 * ldw + st];
+            if (j == J - 1 || j == e_alt) beta = edge[4 * b + (j == J - 1 ? 2 : 3)];
+        }
+    }
     if (on) {
         const double al = Ab[(size_t)(T - 1) * lda_t];
-        Gb[(size_t)(T - 1) * ldo_t] = exp(al + beta - ll);
-        row[(T - 1) & 1][j] = Eb[(size_t)(T - 1) * lde_t] + beta;
+        const double g = exp(al + beta - ll);
+        Gb[(size_t)(T - 1) * ldo_t] = g;
+        const double eb = Eb[(size_t)(T - 1) * lde_t] + beta;
+        row[(T - 1) & 1][j] = eb;
+        if constexpr (ARCS) {
+            x4 = g;
+            if (T == 1) x3 = g;
+            eb1 = eb;
+        }
     }
     double e_next = 0.0, a_next = 0.0;
     if (on && T > 1) {
@@ -388,19 +447,55 @@ __global__ void __launch_bounds__(NT) align_backward_kernel(const double* __rest
         }
         if (on) {
             const double* p = row[(t + 1) & 1];
-            beta = al_lse3(p[j], p[j + 1], st >= 0 ? p[st] : al_ninf());
-            Gb[(size_t)t * ldo_t] = exp(al + beta - ll);
+            if constexpr (ARCS) {
+                if (t + 2 < T) {                                           // the transition into frame t + 2: eb2 = (E + beta)[t + 2][j]
+                    const double* pa = arow[(t + 1) & 1];
+                    x0 += exp(pa[j + 1] + w0 + eb2 - ll);
+                    x1 += exp(pa[j] + w1 + eb2 - ll);
+                    if (sk >= 0) x2 += exp(pa[sk + 1] + w2 + eb2 - ll);
+                }
+                beta = al_lse3(p[j] + w0, p[j + 1] + w1n, st >= 0 ? p[st] + w2s : al_ninf());
+            } else {
+                beta = al_lse3(p[j], p[j + 1], st >= 0 ? p[st] : al_ninf());
+            }
+            const double g = exp(al + beta - ll);
+            Gb[(size_t)t * ldo_t] = g;
             row[t & 1][j] = e + beta;
+            if constexpr (ARCS) {
+                arow[t & 1][j + 1] = al;
+                eb2 = eb1;
+                eb1 = e + beta;
+                if (t == 0) x3 = g;
+            }
+        }
+    }
+    if constexpr (ARCS) {
+        __syncthreads();
+        if (on) {
+            if (T > 1) {                                                   // the transition into frame 1: eb2 = (E + beta)[1][j]
+                const double* pa = arow[0];
+                x0 += exp(pa[j + 1] + w0 + eb2 - ll);
+                x1 += exp(pa[j] + w1 + eb2 - ll);
+                if (sk >= 0) x2 += exp(pa[sk + 1] + w2 + eb2 - ll);
+            }
+            double* X = xi + (size_t)b * ldx_b + (size_t)j * ldx_j;
+            X[0] = x0;
+            X[1] = x1;
+            X[2] = x2;
+            X[3] = x3;
+            X[4] = x4;
         }
     }
 }
 
 // Backpointer code 0 self, 1 next, 2 skip; a later candidate replaces an earlier one only when strictly larger, so the lowest code
 // wins ties; among the end states the lower index wins.  Only adds and compares of the oracle's operands: results are exact.
-template <int NT>
+// ARCS: every candidate carries its arc cost, the start and end states their edge, as in align_forward_kernel.
+template <int NT, bool ARCS>
 __global__ void __launch_bounds__(NT) align_viterbi_kernel(const double* __restrict__ E, long lde_b, long lde_t,
                                                            const int32_t* __restrict__ lens, const int32_t* __restrict__ jlens,
                                                            const int32_t* __restrict__ skip, long ldg, const int32_t* __restrict__ alt,
+                                                           const double* __restrict__ w, long ldw, const double* __restrict__ edge,
                                                            uint8_t* __restrict__ bp, long ldp_b, long ldp_t, int32_t* __restrict__ end,
                                                            double* __restrict__ score, int Tmax, int Jmax) {
     __shared__ double row[2][NT + 1];
@@ -418,9 +513,21 @@ __global__ void __launch_bounds__(NT) align_viterbi_kernel(const double* __restr
     if (sk < 0 || sk >= J) sk = -1;
     const double* Eb = E + (size_t)b * lde_b + j;
     uint8_t* Pb = bp + (size_t)b * ldp_b + j;
+    double w0 = 0.0, w1 = 0.0, w2 = 0.0;
+    if constexpr (ARCS) {
+        if (on) {
+            const double* Wb = w + (size_t)b * 3 * ldw + j;
+            w0 = Wb[0];
+            w1 = Wb[ldw];
+            w2 = Wb[2 * ldw];
+        }
+    }
     if (j == 0) row[0][0] = row[1][0] = al_ninf();
     double a = al_ninf();
-    if (on && (j == 0 || j == s_alt)) a = Eb[0];
+    if (on && (j == 0 || j == s_alt)) {
+        if constexpr (ARCS) a = edge[4 * b + (j == 0 ? 0 : 1)] + Eb[0];
+        else a = Eb[0];
+    }
     if (on) Pb[0] = 0;
     row[0][j + 1] = a;
     double e_next = (on && T > 1) ? Eb[lde_t] : 0.0;
@@ -430,12 +537,12 @@ __global__ void __launch_bounds__(NT) align_viterbi_kernel(const double* __restr
         if (on && t + 1 < T) e_next = Eb[(size_t)(t + 1) * lde_t];
         const double* p = row[(t - 1) & 1];
         if (on) {
-            double best = p[j + 1];
+            double best = ARCS ? p[j + 1] + w0 : p[j + 1];
             int code = 0;
-            const double nx = p[j];
+            const double nx = ARCS ? p[j] + w1 : p[j];
             if (nx > best) { best = nx; code = 1; }
             if (sk >= 0) {
-                const double sv = p[sk + 1];
+                const double sv = ARCS ? p[sk + 1] + w2 : p[sk + 1];
                 if (sv > best) { best = sv; code = 2; }
             }
             a = e + best;
@@ -447,13 +554,23 @@ __global__ void __launch_bounds__(NT) align_viterbi_kernel(const double* __restr
     if (j == 0) {
         const double* p = row[(T - 1) & 1];
         int best_j = J - 1;
-        double best = p[J];
-        if (e_alt >= 0 && e_alt < J - 1 && p[e_alt + 1] >= best) {
-            best_j = e_alt;
-            best = p[e_alt + 1];
+        if constexpr (ARCS) {
+            double best = p[J] + edge[4 * b + 2];
+            if (e_alt >= 0 && e_alt < J - 1 && p[e_alt + 1] + edge[4 * b + 3] >= best) {
+                best_j = e_alt;
+                best = p[e_alt + 1] + edge[4 * b + 3];
+            }
+            end[b] = best_j;
+            score[b] = best;
+        } else {
+            double best = p[J];
+            if (e_alt >= 0 && e_alt < J - 1 && p[e_alt + 1] >= best) {
+                best_j = e_alt;
+                best = p[e_alt + 1];
+            }
+            end[b] = best_j;
+            score[b] = best;
         }
-        end[b] = best_j;
-        score[b] = best;
     }
 }
 
@@ -471,11 +588,34 @@ extern "C" int fs2_align_forward(const double* E, long lde_b, long lde_t, const 
     AL_SCAN_ARGS("align_forward");
     FS2_CHECK_ARG(lda_t >= Jmax && lda_b >= (long)Tmax * lda_t, "align_forward: bad alpha strides %ld %ld", lda_b, lda_t);
     if (B == 0) return FS2_OK;
-#define AL_FWD(NT) align_forward_kernel<NT><<<B, NT, 0, stream>>>(E, lde_b, lde_t, lens, jlens, skip, ldg, alt, alpha, lda_b, lda_t, \
-                                                                  loglik, Tmax, Jmax)
-    if (Jmax <= 256) AL_FWD(256); else if (Jmax <= 512) AL_FWD(512); else AL_FWD(1024);
-#undef AL_FWD
+#define AL_FWD(NT, ARCS, w, ldw, edge)                                                                                             \
+    align_forward_kernel<NT, ARCS><<<B, NT, 0, stream>>>(E, lde_b, lde_t, lens, jlens, skip, ldg, alt, w, ldw, edge, alpha, lda_b,  \
+                                                         lda_t, loglik, Tmax, Jmax)
+    if (Jmax <= 256) AL_FWD(256, false, nullptr, 0, nullptr); else if (Jmax <= 512) AL_FWD(512, false, nullptr, 0, nullptr);
+    else AL_FWD(1024, false, nullptr, 0, nullptr);
     FS2_CHECK_LAUNCH("align_forward");
+    return FS2_OK;
+}
+
+// The scans with arc costs: w [B][3][ldw] (self, next, skip into state j), edge [B][4] (start in 0, start in alt[0], end in J - 1,
+// end in alt[1]); everything else as above.
+#define AL_ARC_ARGS(name)                                                                                                          \
+    FS2_CHECK_ARG(w && edge, name ": null arc costs");                                                                            \
+    FS2_CHECK_ARG(ldw >= Jmax, name ": bad arc cost stride %ld for %d states", ldw, Jmax)
+
+extern "C" int fs2_align_forward_arcs(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens,
+                                      const int32_t* skip, long ldg, const int32_t* alt, const double* w, long ldw, const double* edge,
+                                      double* alpha, long lda_b, long lda_t, double* loglik, int B, int Tmax, int Jmax,
+                                      hipStream_t stream) {
+    FS2_CHECK_ARG(E && lens && jlens && skip && alt && alpha && loglik, "align_forward_arcs: null pointer");
+    AL_SCAN_ARGS("align_forward_arcs");
+    AL_ARC_ARGS("align_forward_arcs");
+    FS2_CHECK_ARG(lda_t >= Jmax && lda_b >= (long)Tmax * lda_t, "align_forward_arcs: bad alpha strides %ld %ld", lda_b, lda_t);
+    if (B == 0) return FS2_OK;
+    if (Jmax <= 256) AL_FWD(256, true, w, ldw, edge); else if (Jmax <= 512) AL_FWD(512, true, w, ldw, edge);
+    else AL_FWD(1024, true, w, ldw, edge);
+#undef AL_FWD
+    FS2_CHECK_LAUNCH("align_forward_arcs");
     return FS2_OK;
 }
 
@@ -489,11 +629,35 @@ extern "C" int fs2_align_backward(const double* E, long lde_b, long lde_t, const
                   "align_backward: bad alpha / gamma strides %ld %ld %ld %ld", lda_b, lda_t, ldo_b, ldo_t);
     FS2_CHECK_ARG(gamma != alpha || (lda_b == ldo_b && lda_t == ldo_t), "align_backward: gamma over alpha needs equal strides");
     if (B == 0) return FS2_OK;
-#define AL_BWD(NT) align_backward_kernel<NT><<<B, NT, 0, stream>>>(E, lde_b, lde_t, lens, jlens, skip, ldg, alt, alpha, lda_b, lda_t, \
-                                                                   loglik, gamma, ldo_b, ldo_t, Tmax, Jmax)
-    if (Jmax <= 256) AL_BWD(256); else if (Jmax <= 512) AL_BWD(512); else AL_BWD(1024);
-#undef AL_BWD
+#define AL_BWD(NT, ARCS, w, ldw, edge, xi, ldx_b, ldx_j)                                                                           \
+    align_backward_kernel<NT, ARCS><<<B, NT, 0, stream>>>(E, lde_b, lde_t, lens, jlens, skip, ldg, alt, w, ldw, edge, alpha, lda_b, \
+                                                          lda_t, loglik, gamma, ldo_b, ldo_t, xi, ldx_b, ldx_j, Tmax, Jmax)
+    if (Jmax <= 256) AL_BWD(256, false, nullptr, 0, nullptr, nullptr, 0, 0);
+    else if (Jmax <= 512) AL_BWD(512, false, nullptr, 0, nullptr, nullptr, 0, 0);
+    else AL_BWD(1024, false, nullptr, 0, nullptr, nullptr, 0, 0);
     FS2_CHECK_LAUNCH("align_backward");
+    return FS2_OK;
+}
+
+// xi [B][Jmax][5] (strides ldx_b, ldx_j): the arc posteriors self, next, skip summed in descending t, then gamma[0][j], gamma[T - 1][j]
+extern "C" int fs2_align_backward_arcs(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens,
+                                       const int32_t* skip, long ldg, const int32_t* alt, const double* w, long ldw,
+                                       const double* edge, const double* alpha, long lda_b, long lda_t, const double* loglik,
+                                       double* gamma, long ldo_b, long ldo_t, double* xi, long ldx_b, long ldx_j, int B, int Tmax,
+                                       int Jmax, hipStream_t stream) {
+    FS2_CHECK_ARG(E && lens && jlens && skip && alt && alpha && loglik && gamma && xi, "align_backward_arcs: null pointer");
+    AL_SCAN_ARGS("align_backward_arcs");
+    AL_ARC_ARGS("align_backward_arcs");
+    FS2_CHECK_ARG(lda_t >= Jmax && lda_b >= (long)Tmax * lda_t && ldo_t >= Jmax && ldo_b >= (long)Tmax * ldo_t,
+                  "align_backward_arcs: bad alpha / gamma strides %ld %ld %ld %ld", lda_b, lda_t, ldo_b, ldo_t);
+    FS2_CHECK_ARG(gamma != alpha || (lda_b == ldo_b && lda_t == ldo_t), "align_backward_arcs: gamma over alpha needs equal strides");
+    FS2_CHECK_ARG(ldx_j >= 5 && ldx_b >= (long)Jmax * ldx_j, "align_backward_arcs: bad xi strides %ld %ld", ldx_b, ldx_j);
+    if (B == 0) return FS2_OK;
+    if (Jmax <= 256) AL_BWD(256, true, w, ldw, edge, xi, ldx_b, ldx_j);
+    else if (Jmax <= 512) AL_BWD(512, true, w, ldw, edge, xi, ldx_b, ldx_j);
+    else AL_BWD(1024, true, w, ldw, edge, xi, ldx_b, ldx_j);
+#undef AL_BWD
+    FS2_CHECK_LAUNCH("align_backward_arcs");
     return FS2_OK;
 }
 
@@ -504,11 +668,28 @@ extern "C" int fs2_align_viterbi(const double* E, long lde_b, long lde_t, const 
     AL_SCAN_ARGS("align_viterbi");
     FS2_CHECK_ARG(ldp_t >= Jmax && ldp_b >= (long)Tmax * ldp_t, "align_viterbi: bad backpointer strides %ld %ld", ldp_b, ldp_t);
     if (B == 0) return FS2_OK;
-#define AL_VIT(NT) align_viterbi_kernel<NT><<<B, NT, 0, stream>>>(E, lde_b, lde_t, lens, jlens, skip, ldg, alt, bp, ldp_b, ldp_t, end, \
-                                                                  score, Tmax, Jmax)
-    if (Jmax <= 256) AL_VIT(256); else if (Jmax <= 512) AL_VIT(512); else AL_VIT(1024);
-#undef AL_VIT
+#define AL_VIT(NT, ARCS, w, ldw, edge)                                                                                             \
+    align_viterbi_kernel<NT, ARCS><<<B, NT, 0, stream>>>(E, lde_b, lde_t, lens, jlens, skip, ldg, alt, w, ldw, edge, bp, ldp_b, ldp_t, \
+                                                         end, score, Tmax, Jmax)
+    if (Jmax <= 256) AL_VIT(256, false, nullptr, 0, nullptr); else if (Jmax <= 512) AL_VIT(512, false, nullptr, 0, nullptr);
+    else AL_VIT(1024, false, nullptr, 0, nullptr);
     FS2_CHECK_LAUNCH("align_viterbi");
+    return FS2_OK;
+}
+
+extern "C" int fs2_align_viterbi_arcs(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens,
+                                      const int32_t* skip, long ldg, const int32_t* alt, const double* w, long ldw, const double* edge,
+                                      uint8_t* bp, long ldp_b, long ldp_t, int32_t* end, double* score, int B, int Tmax, int Jmax,
+                                      hipStream_t stream) {
+    FS2_CHECK_ARG(E && lens && jlens && skip && alt && bp && end && score, "align_viterbi_arcs: null pointer");
+    AL_SCAN_ARGS("align_viterbi_arcs");
+    AL_ARC_ARGS("align_viterbi_arcs");
+    FS2_CHECK_ARG(ldp_t >= Jmax && ldp_b >= (long)Tmax * ldp_t, "align_viterbi_arcs: bad backpointer strides %ld %ld", ldp_b, ldp_t);
+    if (B == 0) return FS2_OK;
+    if (Jmax <= 256) AL_VIT(256, true, w, ldw, edge); else if (Jmax <= 512) AL_VIT(512, true, w, ldw, edge);
+    else AL_VIT(1024, true, w, ldw, edge);
+#undef AL_VIT
+    FS2_CHECK_LAUNCH("align_viterbi_arcs");
     return FS2_OK;
 }
 

@@ -461,6 +461,28 @@ int fs2_align_reduce(const double* partials, long ldp_j, long n_rows, const int3
 int fs2_align_viterbi(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
                       long ldg, const int32_t* alt, uint8_t* bp, long ldp_b, long ldp_t, int32_t* end, double* score, int B, int Tmax,
                       int Jmax, fs2_stream_t stream);
+/* The three scans with a cost on every arc (the "Transitions" paragraph of fastspeech2_amd/align.py).  w [B][3][ldw], ldw >= Jmax:
+ * w[b][0][j] the self arc of state j, w[b][1][j] the arc j - 1 -> j, w[b][2][j] the arc skip[b][j] -> j; edge [B][4]: start in state 0,
+ * start in alt[b][0], end in state jlens[b] - 1, end in alt[b][1].  All costs are finite log-probabilities; nothing of w at
+ * j >= jlens[b] is read.  A null w or edge and ldw < Jmax are FS2_EINVAL before any launch; every other argument is checked as in the
+ * scan without costs.  With all costs 0 each returns the bits of that scan.  Nothing of this has been timed.
+ *   forward:   alpha[0][j] = edge + E[0][j] at the start states; alpha[t][j] = E[t][j] + lse(alpha[t-1][j] + w[0][j],
+ *              alpha[t-1][j-1] + w[1][j], alpha[t-1][skip j] + w[2][j]); loglik = lse over the end states e of alpha[T-1][e] + edge(e)
+ *   backward:  beta[T-1][e] = edge(e), every successor arc adds its cost; gamma as fs2_align_backward (it may be alpha itself);
+ *              xi [B][Jmax][5] (strides ldx_b >= Jmax ldx_j, ldx_j >= 5): xi[b][j][a] = sum over t = T-1 .. 1, in that order, of
+ *              exp(alpha[t-1][pred_a(j)] + w[a][j] + E[t][j] + beta[t][j] - loglik) for a = 0 self, 1 next, 2 skip;
+ *              xi[b][j][3] = gamma[0][j], xi[b][j][4] = gamma[T-1][j]; nothing at j >= jlens[b] is written
+ *   viterbi:   the same costs inside the max, the same tie rules; score includes the end edge */
+int fs2_align_forward_arcs(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                           long ldg, const int32_t* alt, const double* w, long ldw, const double* edge, double* alpha, long lda_b,
+                           long lda_t, double* loglik, int B, int Tmax, int Jmax, fs2_stream_t stream);
+int fs2_align_backward_arcs(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                            long ldg, const int32_t* alt, const double* w, long ldw, const double* edge, const double* alpha,
+                            long lda_b, long lda_t, const double* loglik, double* gamma, long ldo_b, long ldo_t, double* xi,
+                            long ldx_b, long ldx_j, int B, int Tmax, int Jmax, fs2_stream_t stream);
+int fs2_align_viterbi_arcs(const double* E, long lde_b, long lde_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                           long ldg, const int32_t* alt, const double* w, long ldw, const double* edge, uint8_t* bp, long ldp_b,
+                           long ldp_t, int32_t* end, double* score, int B, int Tmax, int Jmax, fs2_stream_t stream);
 /* frames[b][k] = frames the best path spends in block k (block[b][j] = block of state j), zero-filled up to nbmax */
 int fs2_align_backtrack(const uint8_t* bp, long ldp_b, long ldp_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
                         const int32_t* block, long ldg, const int32_t* end, int32_t* frames, int nbmax, int B, int Tmax, int Jmax,
