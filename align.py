@@ -6,7 +6,7 @@ import sys
 
 import yaml
 
-from fastspeech2_amd.align import build
+from fastspeech2_amd.align import build, scores_summary
 
 if __name__ == "__main__":
     parser = argparse.ArgumentParser()
@@ -34,6 +34,9 @@ if __name__ == "__main__":
     parser.add_argument("--transitions", type=int, default=0, choices=(0, 1),
                         help="1: every Baum-Welch pass also trains the self-loop probability of every state and the probabilities of the "
                              "optional silences, and decoding uses them")
+    parser.add_argument("--scores", type=str, default=None,
+                        help="also write per-utterance and per-phone confidence scores (loglik, gop, match) to this JSONL file; no "
+                             "threshold is applied and no TextGrid is dropped")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -48,8 +51,10 @@ if __name__ == "__main__":
                                           fmllr=args.fmllr, fmllr_rounds=args.fmllr_rounds, fmllr_iters=args.fmllr_iters,
                                           fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames,
                                           triphones=args.triphones, tri_iters=args.tri_iters, tri_min_occ=args.tri_min_occ,
-                                          tri_min_gain=args.tri_min_gain, questions=args.questions, transitions=args.transitions)
+                                          tri_min_gain=args.tri_min_gain, questions=args.questions, transitions=args.transitions, scores=args.scores)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))
     print("{} TextGrids written, {} utterances skipped".format(written, len(skipped)))
+    if args.scores is not None:
+        print(scores_summary(args.scores))

@@ -227,11 +227,50 @@ no weight.  The graph topology, the emission stages and the flat start are untou
   Quality against MFA unmeasured (it cannot be run here); transition probabilities are known to matter less than emissions, the
   silence probabilities more; what either changes on real speech is unknown, and no timing measured yet.
 
+Confidence (`scores` = a file; without it every launch, number and TextGrid byte is everything above, unchanged).  Viterbi always
+returns some path: a .lab that does not match its audio (a word misread, skipped or added, a number expanded otherwise, a lexicon's
+first pronunciation that is not the spoken one, an OOV word turned into `spn`) is aligned as confidently as a clean one.  The
+scores below say per phone interval how well the model agrees with what the transcript claims; they are model-based and intrinsic.
+  Feature.  f[t] is the feature the decoding model sees (x, z after `lda`, the adapted fh after `fmllr`), D its dimension, C =
+  `n_classes` at decode time (monophone states, or leaves after `triphones`), M = `mixtures`.
+  Class score.  F[t, c] is the acoustic log-likelihood of frame t under class c in the form of the "Emissions" and "Mixtures"
+  paragraphs: the direct form, multiplied by 1 / var_d, d ascending; with M > 1 the log-sum over ascending m of log w_m + N_m; a
+  component of weight 0 contributes -inf; with M = 1 the weight is 1.  No arc costs enter F.  The kernel takes 1 / var_d and, per
+  component, log w - 1/2 sum_d log(2 pi var_d) (d ascending) once per call, and folds the components with a running maximum, so F
+  agrees with `emit` / `emit_gmm` to rounding, not bit for bit.
+  Path.  s[t] is the state of the Viterbi path at frame t, the path `align` decodes (under the arc costs when `transitions` = 1);
+  p[t] = sid[s[t]] is its class.
+  Per frame.  own[t] = F[t, p[t]];  best[t] = max_c F[t, c];  arg[t] = the lowest c that attains the maximum.  All three come from one
+  kernel and one code path per class: own[t] <= best[t] holds exactly, and own[t] == best[t] bit for bit where arg[t] == p[t].  A
+  class's arithmetic does not depend on its index or on where it sits in a tile: two classes with identical table rows tie bit for
+  bit and the lower index wins (the property the tree paragraph demands of its questions).  The T x C matrix is never stored.
+  Per block (a TextGrid phone interval) of n > 0 frames, sums over ascending t:  `loglik` = (1/n) sum own[t];  `gop` = (1/n) sum
+  (own[t] - best[t]), always <= 0, and 0 when the aligned class wins every frame;  `match` = the share of the block's frames with
+  class_phone[arg[t]] == the block's phone.  class_phone (C,): c // S for monophone states, the phone of the leaf's root for
+  leaves (`Aligner.class_phone`).  `gop` is the goodness of pronunciation of Witt and Young (2000, "Phone-level pronunciation
+  scoring and assessment for interactive language learning") with the free phone loop replaced by the frame-wise maximum over
+  the classes: the usual approximation, and an approximation (the maximum is free to change class at every frame and pays no arc
+  cost, so it is an upper bound of any phone loop's score).  A block of 0 frames has NaN and is not written.
+  Per utterance.  `frames`;  `viterbi` = the Viterbi score / T (the third value `viterbi*` returns; it includes the arc costs when
+  they are trained);  `gop` and `match` = the same means over the frames of all mandatory blocks (`scored_frames` of them): optional
+  `sil` / `sp` are left out, `spn` is included and recognisable by its label;  `loglik` over all frames.
+  fMLLR.  With `fmllr`, `loglik` and `viterbi` are in the adapted space without the Jacobian: they compare within a speaker.  `gop`
+  and `match` are differences and shares, they compare across speakers.
+  File.  One JSON object per written utterance and line: speaker, basename, the utterance numbers, and phones = [label, start_s,
+  end_s, loglik, gop, match] per written interval, the TextGrid's own boundaries.  The block means are taken on the host (numpy) from
+  the per-frame arrays; 28 bytes a frame come back from the device.
+  What is claimed.  Nothing here is a threshold: no default cut-off is shipped, no TextGrid is dropped or changed, and which `gop`
+  separates a wrong transcript from a right one on real speech is unmeasured.  On the synthetic corpus of the tests a substituted
+  word scores below the untouched words of its utterance in all 8 fixed cases; that is all that is known.  The summary line prints
+  the corpus mean and the 10 utterances of lowest `gop` for a person to look at.  Two runs (`triphones` against none, `mixtures`
+  4 against 1) can be compared on how sharply they separate right from wrong transcripts; quality against MFA stays unmeasured.
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
 update runs on the host in numpy.  Every sum's order is a function of the batch shape (for the speaker statistics: and of the
 batch's speaker list) only.  Two runs over one corpus write byte-identical TextGrids.
 """
+import json
 import os
 import re
 from concurrent.futures import ThreadPoolExecutor
@@ -1212,6 +1251,101 @@ def backtrack(bp, lens, G, end):
     return frames
 
 
+def path(bp, lens, G, end):
+    """-> (state, cls): int32 (B, Tmax) on the device, the state of the Viterbi path at every frame and its emission class
+    sid[state]; -1 in both at the frames a broken backpointer chain does not reach, nothing written at t >= T (the buffers start at
+    -1)."""
+    _no_host(bp=bp, end=end)
+    bp = _dev(bp, torch.uint8, "bp")
+    B, Tmax, Jmax = bp.shape
+    if B != len(G.jl) or Jmax < G.Jmax:
+        raise ValueError(f"bp {tuple(bp.shape)} does not hold {len(G.jl)} utterances of up to {G.Jmax} states")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", bp.device)
+    end = _dev(end, torch.int32, "end", 1)
+    if end.shape[0] != B:
+        raise ValueError(f"end holds {end.shape[0]} values for {B} utterances")
+    both = torch.full((2, B, max(Tmax, 1)), -1, dtype=torch.int32, device=bp.device)
+    state, cls = both[0], both[1]
+    _lib.call("fs2_align_path", bp.data_ptr(), bp.stride(0), bp.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.skip.data_ptr(),
+              G.sid.data_ptr(), G.ldg, end.data_ptr(), state.data_ptr(), state.stride(0), cls.data_ptr(), cls.stride(0), B, Tmax, G.Jmax,
+              ops._stream())
+    return state[:, :Tmax], cls[:, :Tmax]
+
+
+def frame_scores(f, lens, cls, w, mu, var, out=None):
+    """Every frame of f (B, Tmax, D) against every class of the mixture tables w (C, M), mu, var (C, M, D) (M = 1: w = 1) -> (own, best
+    float64, arg int32), each (B, Tmax): the score of the frame's own class cls (B, >= Tmax) int32, the largest class score and the
+    lowest class that attains it (the "Confidence" paragraph).  `out` = (own, best, arg) may be strided views of (B, >= Tmax); nothing
+    at t >= T is written (fresh buffers hold NaN / -1 there)."""
+    _no_host(f=f, cls=cls, w=w, mu=mu, var=var)
+    f = _dev(f, torch.float64, "f")
+    B, Tmax, D = f.shape
+    if D == 0:
+        raise ValueError("f has no feature dimension")
+    w, mu, var, M = _check_mix(w, mu, var, D)
+    C = w.shape[0]
+    cls = _dev(cls, torch.int32, "cls", 2)
+    if cls.shape[0] != B or cls.shape[1] < Tmax:
+        raise ValueError(f"cls {tuple(cls.shape)} does not cover f {tuple(f.shape)}")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", f.device)
+    if out is None:
+        own = torch.full((B, max(Tmax, 1)), float("nan"), dtype=torch.float64, device=f.device)
+        best = torch.full_like(own, float("nan"))
+        arg = torch.full((B, max(Tmax, 1)), -1, dtype=torch.int32, device=f.device)
+    else:
+        own, best, arg = out
+        _no_host(own=own, best=best, arg=arg)
+        own, best, arg = _dev(own, torch.float64, "own", 2), _dev(best, torch.float64, "best", 2), _dev(arg, torch.int32, "arg", 2)
+        if any(t.shape[0] != B or t.shape[1] < Tmax for t in (own, best, arg)):
+            raise ValueError(f"own, best and arg must be ({B}, >= {Tmax})")
+    n_ws = _lib.load().fs2_align_frame_scores_ws(C, M, D)
+    if n_ws == 0:
+        raise ValueError(f"tables of {C} classes, {M} components and {D} dimensions exceed the supported size")
+    ws = torch.empty(n_ws, dtype=torch.float64, device=f.device)
+    _lib.call("fs2_align_frame_scores", f.data_ptr(), f.stride(0), f.stride(1), lens_d.data_ptr(), cls.data_ptr(), cls.stride(0),
+              w.data_ptr(), mu.data_ptr(), var.data_ptr(), C, M, D, ws.data_ptr(), n_ws, own.data_ptr(), own.stride(0), best.data_ptr(),
+              best.stride(0), arg.data_ptr(), arg.stride(0), B, Tmax, ops._stream())
+    return own[:, :Tmax], best[:, :Tmax], arg[:, :Tmax]
+
+
+def _ascending_sum(v):
+    """the sum of v in index order (numpy's `sum` adds pairwise)"""
+    return float(np.cumsum(v)[-1]) if len(v) else 0.0
+
+
+def utterance_scores(graph, state, cls, own, best, arg, class_phone, viterbi):
+    """The block and utterance numbers of the "Confidence" paragraph for one utterance from its per-frame arrays (T,): the path's
+    state and class, own, best, arg; `viterbi` is the path's total score.  -> dict(frames, viterbi, loglik, gop, match, blocks
+    (n_blocks, 3) = (loglik, gop, match) per block, NaN for a block of 0 frames)."""
+    T = len(state)
+    blk = np.asarray(graph["block"])[state]
+    diff = own - best
+    hit = (class_phone[arg] == class_phone[cls]).astype(np.float64)
+    blocks = np.full((len(graph["blocks"]), 3), np.nan)
+    edges = np.concatenate([[0], np.nonzero(blk[1:] != blk[:-1])[0] + 1, [T]])
+    for a, b in zip(edges[:-1], edges[1:]):
+        n = float(b - a)
+        blocks[blk[a]] = (_ascending_sum(own[a:b]) / n, _ascending_sum(diff[a:b]) / n, _ascending_sum(hit[a:b]) / n)
+    mand = ~np.array([bl[2] for bl in graph["blocks"]])[blk]
+    n = float(mand.sum())
+    return {"frames": T, "scored_frames": int(n), "viterbi": float(viterbi) / T, "loglik": _ascending_sum(own) / T,
+            "gop": _ascending_sum(diff[mand]) / n, "match": _ascending_sum(hit[mand]) / n, "blocks": blocks}
+
+
+def scores_summary(path, lowest=10):
+    """The summary of a scores file `build(..., scores=path)` wrote: the corpus mean of `gop` over the frames of all mandatory blocks
+    and the `lowest` utterances of lowest `gop`.  It reports; it sets no threshold."""
+    with open(path, encoding="utf-8") as f:
+        rows = [json.loads(line) for line in f if line.strip()]
+    if not rows:
+        return "scores: no utterances"
+    n = [r["scored_frames"] for r in rows]
+    gop, match = (sum(r[k] * m for r, m in zip(rows, n)) / sum(n) for k in ("gop", "match"))
+    worst = sorted(rows, key=lambda r: (r["gop"], r["speaker"], r["basename"]))[:lowest]
+    return (f"scores: {len(rows)} utterances, mean gop {gop:.4f}, mean match {match:.4f} over {sum(n)} frames; lowest gop: " +
+            ", ".join(f"{r['speaker']}/{r['basename']} {r['gop']:.4f}" for r in worst))
+
+
 # ------------------------------------------------------------------------------------------------ the model
 class Aligner:
     """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`.  With `mixtures` = M > 1
@@ -1662,9 +1796,9 @@ class Aligner:
         self.ncomp = ncomp
         return history
 
-    def align(self, feats, lens, graphs, speakers=None):
-        """Viterbi alignment of one ragged batch -> [frames per block (int32 numpy)] per utterance.  `speakers` (with fmllr): the
-        speaker index of every row."""
+    def _decode(self, feats, lens, graphs, speakers):
+        """The feature pipeline and the Viterbi pass `align` and `score` share -> (the features the decoding model sees, lens, the
+        batch's Graphs, backpointers, end states, Viterbi scores)."""
         if self.fmllr and self.W is None:
             raise ValueError("an Aligner with fmllr has no transforms before `fit`")
         speakers = self._speakers(speakers, feats.shape[0], self.n_spk)
@@ -1683,11 +1817,54 @@ class Aligner:
         E = emit(x, lens, G, self.mu, self.var) if self.mixtures == 1 else emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar)
         if self.transitions:
             G.set_arcs(self.loop, self.opt)
-            bp, end, _ = viterbi_arcs(E, lens, G, G.w, G.edge)
+            bp, end, vit = viterbi_arcs(E, lens, G, G.w, G.edge)
         else:
-            bp, end, _ = viterbi(E, lens, G)
+            bp, end, vit = viterbi(E, lens, G)
+        return x, lens, G, bp, end, vit
+
+    def align(self, feats, lens, graphs, speakers=None):
+        """Viterbi alignment of one ragged batch -> [frames per block (int32 numpy)] per utterance.  `speakers` (with fmllr): the
+        speaker index of every row."""
+        _, lens, G, bp, end, _ = self._decode(feats, lens, graphs, speakers)
         frames = backtrack(bp, lens, G, end).cpu().numpy()
         return [frames[b, :len(g["blocks"])].copy() for b, g in enumerate(graphs)]
+
+    def class_phone(self):
+        """(n_classes,) int64: the phone of every emission class at decode time: c // states for monophone states, the phone of the
+        leaf's root after `triphones` (built from `tree`)."""
+        if not self.triphones:
+            return np.arange(self.n_classes, dtype=np.int64) // self.states
+        if self.tree is None:
+            raise ValueError("an Aligner with triphones has no tree before `fit`")
+        t = self.tree
+        out = np.full(t["n_leaves"], -1, np.int64)
+        for root in range(self.n_mono):                                    # the roots are the nodes p S + s
+            todo = [root]
+            while todo:
+                node = todo.pop()
+                if t["leaf"][node] >= 0:
+                    out[t["leaf"][node]] = root // self.states
+                else:
+                    todo += [int(t["yes"][node]), int(t["no"][node])]
+        return out
+
+    def score(self, feats, lens, graphs, speakers=None):
+        """`align` with the confidence scores of the "Confidence" paragraph -> ([frames per block] as `align` returns them,
+        [`utterance_scores` dict per utterance]).  The per-frame arrays (own, best, arg, state, class: 28 bytes a frame) come back
+        from the device, the block and utterance means are taken on the host in ascending t."""
+        x, lens, G, bp, end, vit = self._decode(feats, lens, graphs, speakers)
+        frames = backtrack(bp, lens, G, end).cpu().numpy()
+        state, cls = path(bp, lens, G, end)
+        if self.mixtures == 1:
+            w = torch.ones(self.n_classes, 1, dtype=torch.float64, device=self.device)
+            own, best, arg = frame_scores(x, lens, cls, w, self.mu.unsqueeze(1), self.var.unsqueeze(1))
+        else:
+            own, best, arg = frame_scores(x, lens, cls, self.gw, self.gmu, self.gvar)
+        state, cls, own, best, arg, vit = (v.cpu().numpy() for v in (state, cls, own, best, arg, vit))
+        phone = self.class_phone()
+        out = [utterance_scores(G.graphs[b], state[b, :n], cls[b, :n], own[b, :n], best[b, :n], arg[b, :n], phone, vit[b])
+               for b, n in enumerate(lens)]
+        return [frames[b, :len(g["blocks"])].copy() for b, g in enumerate(graphs)], out
 
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
@@ -1720,9 +1897,11 @@ def fmllr_dim_message(dim, lda):
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
           batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
           fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0,
-          questions=None, transitions=0):
+          questions=None, transitions=0, scores=None):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
-    log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason)."""
+    log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason).  `scores` = a path: decoding goes through
+    `Aligner.score` and one JSON object per written utterance goes to that file (the "Confidence" paragraph): speaker, basename,
+    frames, scored_frames, viterbi, loglik, gop, match and phones = [label, start_s, end_s, loglik, gop, match] per written interval."""
     from . import audio as Audio
     from .preprocess import load_wav
     dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
@@ -1834,11 +2013,25 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     history = aligner.fit([p[:3] for p in packed], iters, [spk_of(p[3]) for p in packed] if fmllr else None)
 
     written = 0
-    for feats, lens, graphs, batch in packed:
-        for i, fr in zip(batch, aligner.align(feats, lens, graphs, spk_of(batch))):
-            e = items[i]["entry"]
-            os.makedirs(os.path.join(out_dir, e[0]), exist_ok=True)
-            wd, ph, xmax = intervals(items[i]["graph"], items[i]["words"], fr, hop, sr)
-            write_textgrid(tg(e), wd, ph, xmax)
-            written += 1
+    sink = open(scores, "w", encoding="utf-8") if scores is not None else None
+    try:
+        for feats, lens, graphs, batch in packed:
+            if sink is None:
+                got, conf = aligner.align(feats, lens, graphs, spk_of(batch)), [None] * len(batch)
+            else:
+                got, conf = aligner.score(feats, lens, graphs, spk_of(batch))
+            for i, fr, sc in zip(batch, got, conf):
+                e = items[i]["entry"]
+                os.makedirs(os.path.join(out_dir, e[0]), exist_ok=True)
+                wd, ph, xmax = intervals(items[i]["graph"], items[i]["words"], fr, hop, sr)
+                write_textgrid(tg(e), wd, ph, xmax)
+                written += 1
+                if sink is not None:
+                    rows = sc["blocks"][np.nonzero(fr)[0]]                 # the written intervals: the blocks with frames
+                    line = {"speaker": e[0], "basename": e[1], **{k: sc[k] for k in ("frames", "scored_frames", "viterbi", "loglik", "gop", "match")},
+                            "phones": [[p, s0, s1] + [float(v) for v in r] for (s0, s1, p), r in zip(ph, rows)]}
+                    sink.write(json.dumps(line, allow_nan=False) + "\n")
+    finally:
+        if sink is not None:
+            sink.close()
     return written, skipped, history

@@ -487,6 +487,27 @@ int fs2_align_viterbi_arcs(const double* E, long lde_b, long lde_t, const int32_
 int fs2_align_backtrack(const uint8_t* bp, long ldp_b, long ldp_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
                         const int32_t* block, long ldg, const int32_t* end, int32_t* frames, int nbmax, int B, int Tmax, int Jmax,
                         fs2_stream_t stream);
+/* Alignment confidence (csrc/fs2_align_score.hip; specification: the "Confidence" paragraph of fastspeech2_amd/align.py).  No atomics.
+ * The walk of fs2_align_backtrack kept per frame: state[b][t] = the state of the best path at frame t, cls[b][t] = sid[b][state]
+ * (int32 [B][Tmax], batch strides lds_b, ldc_b >= Tmax).  A chain that leaves [0, jlens[b]) stops: the frames before it get -1 in
+ * both.  Nothing at t >= lens[b] is written. */
+int fs2_align_path(const uint8_t* bp, long ldp_b, long ldp_t, const int32_t* lens, const int32_t* jlens, const int32_t* skip,
+                   const int32_t* sid, long ldg, const int32_t* end, int32_t* state, long lds_b, int32_t* cls, long ldc_b, int B,
+                   int Tmax, int Jmax, fs2_stream_t stream);
+/* doubles of workspace fs2_align_frame_scores needs: n_classes M (D + 1) (0 for tables outside its limits) */
+int fs2_align_frame_scores_ws(int n_classes, int M, int D);
+/* Every frame of f [B][Tmax][D] (strides ldf_b >= Tmax ldf_t, ldf_t >= D) against every class of the tables w [n_classes * M], mu,
+ * var [n_classes * M][D] (fs2_align_emit_gmm's layout; with M = 1 the caller passes w = 1):  F[t][c] = mx + log(sum_m exp(N_m - mx)),
+ * N_m = log w_m - 1/2 sum_d ((f_d - mu_d)^2 (1 / var_d) + log(2 pi var_d)), d and m ascending, the frame-independent terms taken
+ * once per call into ws.  own[b][t] = F[t][cls[b][t]] (NaN when cls[b][t] is outside [0, n_classes); nothing outside the tables is
+ * read), best[b][t] = max_c F[t][c], arg[b][t] = the lowest c that attains it; own <= best, and own == best bit for bit where
+ * arg == cls.  own, best (double) and arg, cls (int32) are [B][Tmax] with their own batch strides >= Tmax.  Nothing at t >=
+ * lens[b] is read or written.  FS2_EINVAL before any launch: M outside 1..fs2_align_max_mixtures(), D <= 0, n_classes <= 0,
+ * n_classes M (D + 1) >= 2^31, B > 65535, a bad stride, ws_doubles below fs2_align_frame_scores_ws(). */
+int fs2_align_frame_scores(const double* f, long ldf_b, long ldf_t, const int32_t* lens, const int32_t* cls, long ldc_b,
+                           const double* w, const double* mu, const double* var, int n_classes, int M, int D, double* ws,
+                           long ws_doubles, double* own, long ldo_b, double* best, long ldb_b, int32_t* arg, long lda_b, int B,
+                           int Tmax, fs2_stream_t stream);
 /* The LDA stage (csrc/fs2_align_lda.hip).  Spliced frames y [B][Tmax][D_s], D_s = n_mel (2 c + 1), strides ldy_b >= Tmax ldy_t,
  * ldy_t >= D_s, in elements.  Limits, all FS2_EINVAL before any launch: 0 <= c <= 4, 1 <= k <= D_s <= fs2_align_max_splice_dim() (720).
  * Nothing at t >= lens[b] is read or written.  No atomics. */
