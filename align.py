@@ -37,6 +37,8 @@ if __name__ == "__main__":
     parser.add_argument("--scores", type=str, default=None,
                         help="also write per-utterance and per-phone confidence scores (loglik, gop, match) to this JSONL file; no "
                              "threshold is applied and no TextGrid is dropped")
+    parser.add_argument("--g2p_model", type=str, default=None,
+                        help="a model trained by `python g2p.py train`: an out-of-lexicon word gets its pronunciation instead of spn")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -51,7 +53,8 @@ if __name__ == "__main__":
                                           fmllr=args.fmllr, fmllr_rounds=args.fmllr_rounds, fmllr_iters=args.fmllr_iters,
                                           fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames,
                                           triphones=args.triphones, tri_iters=args.tri_iters, tri_min_occ=args.tri_min_occ,
-                                          tri_min_gain=args.tri_min_gain, questions=args.questions, transitions=args.transitions, scores=args.scores)
+                                          tri_min_gain=args.tri_min_gain, questions=args.questions, transitions=args.transitions, scores=args.scores,
+                                          g2p=args.g2p_model)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))

@@ -304,6 +304,17 @@ def words_of(text):
     return [w for w in pieces if w]
 
 
+def pronounce_oov(transcripts, lexicon, phone_ids, g2p):
+    """Out-of-lexicon words through a trained grapheme-to-phoneme model (fastspeech2_amd/g2p.py): every word of `transcripts` (lists of
+    words) that `lexicon` lacks is pronounced in ONE batched decode; a pronunciation is taken when the model has one and every phone
+    of it is in `phone_ids`, else the word stays out (and becomes `spn`).  -> (lexicon with the taken words added, taken, left)."""
+    oov = sorted({w.lower() for words in transcripts for w in words} - set(lexicon))
+    if not oov:
+        return lexicon, 0, 0
+    said = {w: p for w, p in zip(oov, g2p.pronounce(oov)) if p and all(q in phone_ids for q in p)}
+    return {**lexicon, **said}, len(said), len(oov) - len(said)
+
+
 def phone_table(lexicon):
     """phone -> id over the lexicon's phones, sorted, then sil, sp, spn."""
     phones = sorted({p for ps in lexicon.values() for p in ps} - {SIL, SP, SPN})
@@ -1897,11 +1908,13 @@ def fmllr_dim_message(dim, lda):
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
           batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
           fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0,
-          questions=None, transitions=0, scores=None):
+          questions=None, transitions=0, scores=None, g2p=None):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason).  `scores` = a path: decoding goes through
     `Aligner.score` and one JSON object per written utterance goes to that file (the "Confidence" paragraph): speaker, basename,
-    frames, scored_frames, viterbi, loglik, gop, match and phones = [label, start_s, end_s, loglik, gop, match] per written interval."""
+    frames, scored_frames, viterbi, loglik, gop, match and phones = [label, start_s, end_s, loglik, gop, match] per written interval.
+    `g2p` = a `fastspeech2_amd.g2p.G2P` model or the path of one: out-of-lexicon words get its pronunciation instead of `spn`
+    (`pronounce_oov`, one batched decode of the corpus's OOV words before any graph is built); the count is printed."""
     from . import audio as Audio
     from .preprocess import load_wav
     dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
@@ -1948,6 +1961,17 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     existing = [e for e in entries if os.path.exists(tg(e))]
     if existing and not overwrite:
         raise FileExistsError(f"{len(existing)} TextGrids exist already (first: {tg(existing[0])}); pass --overwrite to replace them")
+
+    if g2p is not None:
+        if isinstance(g2p, str):
+            from .g2p import G2P
+            g2p = G2P.load(g2p, dev)
+        transcripts = []
+        for e in entries:
+            with open(os.path.join(raw, e[0], e[1] + ".lab"), encoding="utf-8") as f:
+                transcripts.append(words_of(f.readline()))
+        lexicon, taken, left = pronounce_oov(transcripts, lexicon, phone_ids, g2p)
+        print(f"{taken} out-of-lexicon words pronounced by the g2p model, {left} left as {SPN}")
 
     def read(e):
         wav = np.clip(load_wav(os.path.join(raw, e[0], e[1] + ".wav"), sr), -1.0, 1.0).astype(np.float32)

@@ -678,6 +678,57 @@ int fs2_adam_step_h(float* p, float* g, float* m, float* v, size_t n, const floa
                     float bc2, float b1, float b2, float eps, float wd, void* p_lowp, int lowp_dtype, int zero_grad,
                     fs2_stream_t stream);
 
+/* ---- grapheme-to-phoneme: graphone n-gram, many-to-many EM alignment and beam search (specification: fastspeech2_amd/g2p.py) ----
+ * fp64 throughout, ragged batches of words: word w has glens[w] letters (index i) and plens[w] phones (index j), int32 on the
+ * device, ids in int32 rows letters [W][ldl] and phones [W][ldp]; an id outside [0, A) / [0, P) makes every arc over it absent.
+ * Arc code c consumes (letters, phones) = (1,0), (1,1), (1,2), (2,1).  logtheta is the dense table of A NQ + A A P doubles,
+ * NQ = 1 + P + P P: codes 0..2 at a NQ + q (q = 0 | 1 + p | 1 + P + p0 P + p1), code 3 at A NQ + (a0 A + a1) P + p; n_table must be
+ * exactly that and at most fs2_g2p_max_table_mib() MiB.  Limits, FS2_EINVAL before any launch: A <= fs2_g2p_max_letters() (64),
+ * P <= fs2_g2p_max_phones() (128), Lgmax <= fs2_g2p_max_word_letters() (32), Lpmax <= fs2_g2p_max_word_phones() (48), beam K <=
+ * fs2_g2p_max_beam() (256), order N <= fs2_g2p_max_order() (4).  Nothing at i >= glens[w] or j >= plens[w] of an id row is read,
+ * nothing outside a word's own cells is written.  No atomics; every sum has one order.  Nothing of this has been timed. */
+int fs2_g2p_max_letters(void);
+int fs2_g2p_max_phones(void);
+int fs2_g2p_max_word_letters(void);
+int fs2_g2p_max_word_phones(void);
+int fs2_g2p_max_beam(void);
+int fs2_g2p_max_order(void);
+int fs2_g2p_max_table_mib(void);
+/* log-domain forward / backward over the (Lg + 1) x (Lp + 1) lattice, the log-sum-exp in arc-code order: loglik[w] (-inf without a
+ * path) and post[w][i][j][c], i < Lg, j <= Lp (strides ldo_w >= Lgmax ldo_i, ldo_i >= 4 (Lpmax + 1)), the posterior of the arc of
+ * code c that leaves cell (i, j): exactly 0 when the arc does not exist or lies on no path, never NaN */
+int fs2_g2p_m2m_expect(const int32_t* letters, long ldl, const int32_t* phones, long ldp, const int32_t* glens, const int32_t* plens,
+                       const double* logtheta, long n_table, int A, int P, double* loglik, double* post, long ldo_w, long ldo_i, int W,
+                       int Lgmax, int Lpmax, fs2_stream_t stream);
+/* the same lattice with max: score[w] the best path's log weight (-inf without one), bp[w][i][j], i <= Lg, j <= Lp (strides ldb_w >=
+ * (Lgmax + 1) ldb_i, ldb_i >= Lpmax + 1), the code of the best arc into (i, j), the lowest on ties, 255 at (0, 0) and at a cell no
+ * path reaches */
+int fs2_g2p_m2m_viterbi(const int32_t* letters, long ldl, const int32_t* phones, long ldp, const int32_t* glens, const int32_t* plens,
+                        const double* logtheta, long n_table, int A, int P, double* score, uint8_t* bp, long ldb_w, long ldb_i, int W,
+                        int Lgmax, int Lpmax, fs2_stream_t stream);
+/* The back-off n-gram: order n <= N holds the entries [order_offs[n - 1], order_offs[n]) of keys / logp / bow (n_keys in all), keys
+ * ascending, a key packing n ids of 16 bits with the oldest in the highest place.  out[q] = log P(tok[q] | hist[q][0 .. N - 1)),
+ * the history oldest first (ldh >= N - 1): found at order n -> its logp; else bow of the order's history (0 when that history has
+ * no entry) + the score under the history without its oldest id; -inf when the token has no unigram.  The weights are added from
+ * the longest history down, the log-probability last. */
+int fs2_g2p_ngram_score(const int32_t* hist, long ldh, const int32_t* tok, const uint64_t* keys, const double* logp, const double* bow,
+                        const int32_t* order_offs, int n_keys, int N, double* out, int n, fs2_stream_t stream);
+/* Beam search, one workgroup per word, synchronous in the letter position, no recombination.  Graphone types are 0 .. T - 1 (T <
+ * 65534), <s> = T, </s> = T + 1; type_phones [T][2] their phones (-1 = none); spell_offs [A + A A + 1] / spell_types [n_spell] list
+ * per letter chunk (a | A + a0 A + a1) the ascending types that spell it, a row cut at max_fan1 (one letter) / max_fan2 (two).
+ * Hypotheses at position i expand those at i - 1 by the types spelling letters[i-1:i], then those at i - 2 by the types spelling
+ * letters[i-2:i]; candidates are numbered in that order, parent slot ascending, type ascending; the K best are kept, ties to the
+ * lower number, -inf dropped.  Caller's workspace, readable afterwards: beam_score / beam_hist / beam_bp [W][Lgmax + 1][K] (hist =
+ * the last three ids packed like a key, bp = 2 (parent slot) + letters consumed - 1), beam_n [W][Lgmax + 1] the kept counts, cand
+ * [W][ldc], ldc >= K (max_fan1 + max_fan2).  At the end log P(</s> | history) is added and the best (the lower slot on ties) is
+ * walked back: out_phones[w][0 .. out_n[w]) (ldo >= 2 Lgmax), out_score[w]; out_n[w] = -1 and -inf when nothing reaches the end
+ * (an unknown letter, an unseen spelling). */
+int fs2_g2p_decode(const int32_t* letters, long ldl, const int32_t* glens, int A, const int32_t* spell_offs, const int32_t* spell_types,
+                   int n_spell, int max_fan1, int max_fan2, const int32_t* type_phones, int T, const uint64_t* keys, const double* logp,
+                   const double* bow, const int32_t* order_offs, int n_keys, int N, int K, double* beam_score, uint64_t* beam_hist,
+                   int32_t* beam_bp, int32_t* beam_n, double* cand, long ldc, int32_t* out_phones, long ldo, int32_t* out_n,
+                   double* out_score, int W, int Lgmax, fs2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,8 @@ With --griffin_iters N the wavs come from N Griffin-Lim iterations on the post-n
 Batch mode reads phoneme strings (the `{...}` field of train.txt / val.txt), exactly what the reference's TextDataset
 does.  Single mode takes the phoneme string directly: the grapheme-to-phoneme step of the reference (g2p_en / pypinyin +
 lexicon, synthesize.py:20-84) is host-side string processing outside the hot path and its packages are not in this
-image, so raw text without braces is rejected with a clear message instead of being silently mis-read.
+image, so raw text without braces is rejected with a clear message instead of being silently mis-read, unless --g2p_model names
+a model trained by `python g2p.py train` (fastspeech2_amd/g2p.py): then English free text is pronounced with the lexicon and that model.
 With WORLD_SIZE > 1 (torch.distributed.run) the source list is sharded across GPUs: replicas only, no collective.
 """
 import argparse
@@ -60,7 +61,29 @@ def synthesize_griffin_lim(model, configs, batchs, control_values, n_iters, devi
     return n
 
 
+def free_text(args, preprocess_config):
+    """--g2p_model: English free text -> the braced phoneme string.  Lexicon words keep their lexicon phones, any other word gets the
+    trained graphone model's (fastspeech2_amd/g2p.py), punctuation becomes `sp`; what the model cannot pronounce is left out."""
+    from fastspeech2_amd.align import read_lexicon
+    from fastspeech2_amd.g2p import G2P, text_to_phones
+    if preprocess_config["preprocessing"]["text"]["language"] != "en":
+        raise SystemExit("--g2p_model pronounces English text only (preprocessing.text.language is not en)")
+    model = G2P.load(args.g2p_model, torch.device("cuda", torch.cuda.current_device()))
+    phones, dropped = text_to_phones(args.text, read_lexicon(preprocess_config["path"]["lexicon_path"]), model)
+    if dropped:
+        print("warning: no pronunciation for {} (left out; numbers and abbreviations are not expanded)".format(", ".join(dropped)))
+    print("Raw Text Sequence: {}".format(args.text))
+    print("Phoneme Sequence: {}".format(phones))
+    return phones
+
+
 def single_batch(args, preprocess_config):
+    if args.g2p_model is not None and not re.search(r"\{.+?\}", args.text):
+        raw = args.text
+        args.text = free_text(args, preprocess_config)
+        texts = np.array([np.array(text_to_sequence(args.text, preprocess_config["preprocessing"]["text"]["text_cleaners"]))])
+        ids = raw_texts = [raw[:100].replace(" ", "_")]
+        return [(ids, raw_texts, np.array([args.speaker_id]), texts, np.array([len(texts[0])]), len(texts[0]))]
     if not re.search(r"\{.+?\}", args.text):
         raise SystemExit("--mode single expects a phoneme string in braces, e.g. --text \"{HH AH0 L OW1 sp W ER1 L D}\" "
                          "(grapheme-to-phoneme conversion needs g2p_en/pypinyin, which this build does not ship)")
@@ -96,6 +119,8 @@ def parse_args(argv=None):
                         help="vocoder.model MelGAN: directory with linda_johnson.pt / multi_speaker.pt (after a torch.hub run of the "
                              "reference they lie in ~/.cache/torch/hub/descriptinc_melgan-neurips_master/models/)")
     parser.add_argument("--random_vocoder", action="store_true", help="allow a random-init vocoder when no checkpoint exists (smoke runs)")
+    parser.add_argument("--g2p_model", default=None,
+                        help="a model trained by `python g2p.py train`: --mode single takes free English text (without it, a phoneme string in braces)")
     parser.add_argument("--griffin_iters", type=int, default=0,
                         help="N > 0: waveforms by N Griffin-Lim iterations on the post-net mel (float32 wavs, no vocoder loaded); 0 = HiFi-GAN")
     return parser.parse_args(argv)
