@@ -37,6 +37,9 @@ if __name__ == "__main__":
     parser.add_argument("--scores", type=str, default=None,
                         help="also write per-utterance and per-phone confidence scores (loglik, gop, match) to this JSONL file; no "
                              "threshold is applied and no TextGrid is dropped")
+    parser.add_argument("--seg_scores", type=int, default=0, choices=(0, 1),
+                        help="1 (needs --scores): also score every interval as a whole HMM of every phone and add gop_seg (Witt and "
+                             "Young's definition), the best rival phone and the margin to every phone entry")
     parser.add_argument("--g2p_model", type=str, default=None,
                         help="a model trained by `python g2p.py train`: an out-of-lexicon word gets its pronunciation instead of spn")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
@@ -45,6 +48,8 @@ if __name__ == "__main__":
     parser.add_argument("--num_workers", type=int, default=8, help="host threads reading wav and .lab files")
     args = parser.parse_args()
 
+    if args.seg_scores and args.scores is None:
+        parser.error("--seg_scores 1 needs --scores FILE")
     config = yaml.load(open(args.config, "r"), Loader=yaml.FullLoader)
     try:
         written, skipped, history = build(config, device=args.device, states=args.states, iters=args.iters, overwrite=args.overwrite,
@@ -54,7 +59,7 @@ if __name__ == "__main__":
                                           fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames,
                                           triphones=args.triphones, tri_iters=args.tri_iters, tri_min_occ=args.tri_min_occ,
                                           tri_min_gain=args.tri_min_gain, questions=args.questions, transitions=args.transitions, scores=args.scores,
-                                          g2p=args.g2p_model)
+                                          g2p=args.g2p_model, seg_scores=args.seg_scores)
     except FileExistsError as e:
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))

@@ -265,6 +265,47 @@ scores below say per phone interval how well the model agrees with what the tran
   the corpus mean and the 10 utterances of lowest `gop` for a person to look at.  Two runs (`triphones` against none, `mixtures`
   4 against 1) can be compared on how sharply they separate right from wrong transcripts; quality against MFA stays unmeasured.
 
+Segmental scores (`seg_scores` = 1, needs `scores`; without it every launch, number, TextGrid byte and scores-file byte is everything
+above, unchanged).  `gop` above replaces Witt and Young's denominator, the best phone hypothesis for the segment, by a maximum that
+may change class at every frame and pays no arc cost: an upper bound that does not say which phone the model would rather have
+heard.  This paragraph is the definition as published (Witt and Young 2000, eq. 3): log p(O_seg | p) minus max_q log p(O_seg | q)
+over the number of frames, every q scored as a whole HMM over the same segment, and it names the winning q.
+  Segment.  Block k of an utterance with n > 0 frames [a, a + n) on the decoded Viterbi path (`segment_table`); the blocks partition
+  the frames.
+  Candidates (`Aligner.candidates`).  P is the number of phones of the phone table (`sil`, `sp` and `spn` included), S the states
+  per phone.  For every block k, phone q < P and state s < S the candidate class cand[k, q, s] is q S + s for monophone models and,
+  after `triphones`, the leaf that (l_k, q, r_k, s) reaches from root q S + s.  l_k and r_k are the block's own transcript contexts
+  as `triphone_contexts` gives them; l = r = `#` when the block's phone or q is one of the context-independent `sil` / `sp` / `spn`.
+  Only the block's own states are substituted, its neighbours keep their transcript contexts: an approximation (a rival phone
+  would also change the context of the phones beside it).
+  Class score.  F[t, c] exactly as in the Confidence paragraph: the direct form, 1 / var_d and the per-component constant prepared
+  once per call, d ascending, the mixture fold with a running maximum, a component of weight 0 contributing -inf.
+  Segment score.  With c_s = cand[k, q, s]:  ws_s = log loop[c_s] and wn_s = log(1 - loop[c_s]) when `transitions` = 1, both 0
+  otherwise.  v_0(a) = F[a, c_0] and v_s(a) = -inf for s > 0;  v_s(t) = F[t, c_s] + max(v_s(t-1) + ws_s, v_{s-1}(t-1) + wn_{s-1});
+  V[k, q] = v_{S-1}(a + n - 1) + wn_{S-1}, -inf when n < S.  This is the block's own topology: no skip inside a block, every state
+  occupied at least one frame.  The exit arc is included because it differs per candidate; the entry costs (`opt`) are the same
+  for all candidates and are left out.
+  Per written interval, p the interval's phone.  `rival` = the lowest q != p that attains max_{q != p} V[k, q];  `margin` = (V[k, p] -
+  V[k, rival]) / n, positive when the transcript's phone wins;  `gop_seg` = min(margin, 0), Witt and Young's number, always <= 0.
+  With P = 1 there is no rival: null, null and 0 are written.
+  Per utterance.  `gop_seg` = the frame-weighted mean over the mandatory blocks, the frames `gop` uses.
+  Relations.  V[k, p] >= the forced path's own score over the segment, sum own[t] plus its internal and exit arcs, and equal to it
+  up to rounding unless the segment has a tie (the forced path is the best path through the block's states; its entry and the
+  rest of the utterance do not depend on how the block's frames are shared out).  Without `transitions`: gop <= gop_seg <= 0 per
+  block up to rounding, since sum best[t] bounds every V[k, q] from above and V[k, p] bounds the own sum from above.
+  Kernel (csrc/fs2_align_seg.hip).  One workgroup per (utterance, block); F is computed for 16 frames x 64 candidate columns at a
+  time with the statements of the frame-score kernel and one lane per candidate phone advances v over the frames, so a class's
+  arithmetic does not depend on where it sits: two phones with identical table rows get bit-identical V and the lower one is the
+  rival.  No floating-point atomics; every sum ascends in t and d: two runs are bit-identical.  A segment with frames <= 0, start <
+  0 or start + frames > T, or a candidate row holding -1, is absent: its V row keeps the NaN of a fresh buffer.  A candidate class
+  >= n_classes is a ValueError before the launch (the kernel scores such a column -inf without reading the table); P above
+  `max_seg_phones()` (256), S outside 1..3 and M outside 1..8 are ValueErrors (FS2_EINVAL) before the launch.
+  File.  Every phone entry becomes [label, start_s, end_s, loglik, gop, match, gop_seg, rival_label, margin] and the utterance object
+  gains `gop_seg`; the summary appends the corpus mean `gop_seg` and the 20 most frequent (phone -> rival) pairs among the
+  intervals with margin < 0, with their counts.
+  What is claimed.  The published definition, pinned to a numpy restatement (tests/align_seg_ref.py).  No threshold.  Nothing has
+  been measured on real speech, against MFA or against Kaldi's `compute-gop`, and no timing measured yet.
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
 update runs on the host in numpy.  Every sum's order is a function of the batch shape (for the speaker statistics: and of the
@@ -1353,8 +1394,107 @@ def scores_summary(path, lowest=10):
     n = [r["scored_frames"] for r in rows]
     gop, match = (sum(r[k] * m for r, m in zip(rows, n)) / sum(n) for k in ("gop", "match"))
     worst = sorted(rows, key=lambda r: (r["gop"], r["speaker"], r["basename"]))[:lowest]
-    return (f"scores: {len(rows)} utterances, mean gop {gop:.4f}, mean match {match:.4f} over {sum(n)} frames; lowest gop: " +
+    text = (f"scores: {len(rows)} utterances, mean gop {gop:.4f}, mean match {match:.4f} over {sum(n)} frames; lowest gop: " +
             ", ".join(f"{r['speaker']}/{r['basename']} {r['gop']:.4f}" for r in worst))
+    if all("gop_seg" in r for r in rows):                                  # written with `seg_scores`
+        seg = sum(r["gop_seg"] * m for r, m in zip(rows, n)) / sum(n)
+        pairs = {}
+        for r in rows:
+            for p in r["phones"]:
+                if p[8] is not None and p[7] is not None and p[8] < 0:
+                    pairs[p[0], p[7]] = pairs.get((p[0], p[7]), 0) + 1
+        top = sorted(pairs.items(), key=lambda kv: (-kv[1], kv[0]))[:20]
+        text += (f"; mean gop_seg {seg:.4f}; intervals that lose to a rival: {sum(pairs.values())}" +
+                 ("; most frequent: " + ", ".join(f"{p} -> {q} {c}" for (p, q), c in top) if top else ""))
+    return text
+
+
+def max_seg_phones():
+    return _lib.load().fs2_align_max_seg_phones()
+
+
+def segment_scores(f, lens, seg, cand, w, mu, var, arc, out=None):
+    """Every segment seg (B, Kmax, 2) int32 = (start, frames) of f (B, Tmax, D) as a whole HMM of every candidate phone: cand (B, Kmax,
+    P, S) int32 holds the class of every state of every candidate, arc (C, 2) = (log stay, log leave) per class of the mixture
+    tables w (C, M), mu, var (C, M, D) -> V (B, Kmax, P) float64 (the "Segmental scores" paragraph).  `out` may be a strided view of
+    (B, Kmax, >= P); the row of an absent segment (frames <= 0, outside the utterance, a negative candidate) is not written (a
+    fresh buffer holds NaN there).  A candidate class >= C is a ValueError before the launch."""
+    _no_host(f=f, seg=seg, cand=cand, w=w, mu=mu, var=var, arc=arc)
+    f = _dev(f, torch.float64, "f")
+    B, Tmax, D = f.shape
+    if D == 0:
+        raise ValueError("f has no feature dimension")
+    w, mu, var, M = _check_mix(w, mu, var, D)
+    C = w.shape[0]
+    seg, cand = _dev(seg, torch.int32, "seg").contiguous(), _dev(cand, torch.int32, "cand", 4).contiguous()
+    Kmax, P, S = cand.shape[1:]
+    if seg.shape != (B, Kmax, 2) or cand.shape[0] != B:
+        raise ValueError(f"seg {tuple(seg.shape)} and cand {tuple(cand.shape)} do not describe the blocks of {B} utterances")
+    if not 1 <= P <= max_seg_phones() or not 1 <= S <= 3:
+        raise ValueError(f"{P} candidate phones of {S} states, supported are 1..{max_seg_phones()} phones of 1..3 states")
+    arc = _dev(arc, torch.float64, "arc", 2).contiguous()
+    if arc.shape != (C, 2):
+        raise ValueError(f"arc {tuple(arc.shape)} is not ({C}, 2)")
+    if cand.numel() and int(cand.max()) >= C:
+        raise ValueError(f"cand holds class {int(cand.max())}, the tables have {C}")
+    _, lens_d = ragged.lengths(lens, B, Tmax, "lens", f.device)
+    if out is None:
+        V = torch.full((B, max(Kmax, 1), P), float("nan"), dtype=torch.float64, device=f.device)
+    else:
+        _no_host(out=out)
+        V = _dev(out, torch.float64, "out")
+        if V.shape[0] != B or V.shape[1] < Kmax or V.shape[2] < P or (V.numel() and V.stride(0) < V.shape[1] * V.stride(1)):
+            raise ValueError(f"out must be ({B}, >= {Kmax}, >= {P}), got {tuple(V.shape)}")
+    n_ws = _lib.load().fs2_align_segment_scores_ws(C, M, D)
+    if n_ws == 0:
+        raise ValueError(f"tables of {C} classes, {M} components and {D} dimensions exceed the supported size")
+    ws = torch.empty(n_ws, dtype=torch.float64, device=f.device)
+    _lib.call("fs2_align_segment_scores", f.data_ptr(), f.stride(0), f.stride(1), lens_d.data_ptr(), seg.data_ptr(), seg.stride(0),
+              cand.data_ptr(), cand.stride(0), cand.stride(1), w.data_ptr(), mu.data_ptr(), var.data_ptr(), C, M, D, arc.data_ptr(),
+              ws.data_ptr(), n_ws, V.data_ptr(), V.stride(0), V.stride(1), B, Tmax, Kmax, P, S, ops._stream())
+    return V[:, :Kmax, :P]
+
+
+def segment_table(graph, state):
+    """(n_blocks, 2) int32 = (start, frames) of every block on the per-frame path `state` (T,); a block the path skips is (0, 0)."""
+    blk = np.asarray(graph["block"])[state]
+    out = np.zeros((len(graph["blocks"]), 2), np.int32)
+    edges = np.concatenate([[0], np.nonzero(blk[1:] != blk[:-1])[0] + 1, [len(blk)]])
+    for a, b in zip(edges[:-1], edges[1:]):
+        out[blk[a]] = (a, b - a)
+    return out
+
+
+def block_phones(graph):
+    """The phone id of every block of a monophone graph (`utterance_graph`: state k S + s has class phone_id S + s)."""
+    S = len(graph["sid"]) // len(graph["blocks"])
+    return np.asarray(graph["sid"], np.int64)[::S] // S
+
+
+def segment_reductions(graph, seg, V):
+    """The block and utterance numbers of the "Segmental scores" paragraph for the monophone graph of one utterance from seg
+    (n_blocks, 2) and V (n_blocks, P) -> (blocks (n_blocks, 3) = (gop_seg, rival, margin), NaN for a block of 0 frames; the
+    utterance's gop_seg, the mean over the frames of the mandatory blocks in block order)."""
+    out = np.full((len(graph["blocks"]), 3), np.nan)
+    num, den, phones = 0.0, 0.0, block_phones(graph)
+    for k, (_, _, optional) in enumerate(graph["blocks"]):
+        n = int(seg[k, 1])
+        if n == 0:
+            continue
+        if V.shape[1] == 1:
+            out[k, 2] = 0.0
+            continue
+        p = int(phones[k])
+        rest = V[k].copy()
+        rest[p] = -np.inf
+        rival = int(np.argmax(rest))                                       # the first of the largest
+        if rival == p:                                                     # every rival at -inf: the lowest q != p
+            rival = 1 if p == 0 else 0
+        margin = (V[k, p] - V[k, rival]) / n
+        out[k] = (min(margin, 0.0), rival, margin)
+        if not optional:
+            num, den = num + out[k, 0] * n, den + n
+    return out, num / den if den else float("nan")
 
 
 # ------------------------------------------------------------------------------------------------ the model
@@ -1859,33 +1999,71 @@ class Aligner:
                     todo += [int(t["yes"][node]), int(t["no"][node])]
         return out
 
-    def score(self, feats, lens, graphs, speakers=None):
+    def candidates(self, graph):
+        """(n_blocks, P S) int32: the candidate classes of the "Segmental scores" paragraph for the monophone graph of one utterance:
+        q S + s, or after `triphones` the leaf of (l_k, q, r_k, s), the block's own contexts (`#` on both sides when the block's
+        phone or q is context-independent)."""
+        S, P, K = self.states, self.n_mono // self.states, len(graph["blocks"])
+        if not self.triphones:
+            return np.tile(np.arange(P * S, dtype=np.int32), (K, 1))
+        if self.tree is None:
+            raise ValueError("an Aligner with triphones has no tree before `fit`")
+        ctx = triphone_contexts(graph, self.phone_ids, S)[::S]            # (l, p, r, 0) of every block
+        bnd, ci = len(self.phone_ids), [self.phone_ids[p] for p in (SIL, SP, SPN)]
+        free = np.isin(ctx[:, 1], ci)[:, None] | np.isin(np.arange(P), ci)[None, :]
+        keys = np.empty((K, P, S, 4), np.int64)                            # (p, s, l, r), the order `tree_leaves` takes
+        keys[..., 0] = np.arange(P)[None, :, None]
+        keys[..., 1] = np.arange(S)[None, None, :]
+        keys[..., 2] = np.where(free, bnd, ctx[:, 0][:, None])[:, :, None]
+        keys[..., 3] = np.where(free, bnd, ctx[:, 2][:, None])[:, :, None]
+        t = self.tree
+        return tree_leaves(t["question"], t["yes"], t["no"], t["leaf"], t["member"], keys, S).reshape(K, P * S).astype(np.int32)
+
+    def score(self, feats, lens, graphs, speakers=None, segmental=False):
         """`align` with the confidence scores of the "Confidence" paragraph -> ([frames per block] as `align` returns them,
         [`utterance_scores` dict per utterance]).  The per-frame arrays (own, best, arg, state, class: 28 bytes a frame) come back
-        from the device, the block and utterance means are taken on the host in ascending t."""
+        from the device, the block and utterance means are taken on the host in ascending t.  `segmental`: every dict also gets
+        the numbers of the "Segmental scores" paragraph: `seg` (n_blocks, 3) = (gop_seg, rival, margin) per block, NaN for a block
+        of 0 frames, `V` (n_blocks, P) and the utterance's `gop_seg`; without it nothing more is launched or returned."""
         x, lens, G, bp, end, vit = self._decode(feats, lens, graphs, speakers)
         frames = backtrack(bp, lens, G, end).cpu().numpy()
         state, cls = path(bp, lens, G, end)
         if self.mixtures == 1:
-            w = torch.ones(self.n_classes, 1, dtype=torch.float64, device=self.device)
-            own, best, arg = frame_scores(x, lens, cls, w, self.mu.unsqueeze(1), self.var.unsqueeze(1))
+            tables = (torch.ones(self.n_classes, 1, dtype=torch.float64, device=self.device), self.mu.unsqueeze(1), self.var.unsqueeze(1))
         else:
-            own, best, arg = frame_scores(x, lens, cls, self.gw, self.gmu, self.gvar)
+            tables = (self.gw, self.gmu, self.gvar)
+        own, best, arg = frame_scores(x, lens, cls, *tables)
         state, cls, own, best, arg, vit = (v.cpu().numpy() for v in (state, cls, own, best, arg, vit))
         phone = self.class_phone()
         out = [utterance_scores(G.graphs[b], state[b, :n], cls[b, :n], own[b, :n], best[b, :n], arg[b, :n], phone, vit[b])
                for b, n in enumerate(lens)]
+        if segmental:
+            S, P = self.states, self.n_mono // self.states
+            seg = np.zeros((len(graphs), max(G.nbmax, 1), 2), np.int32)
+            cand = np.full((len(graphs), max(G.nbmax, 1), P * S), -1, np.int32)
+            for b, (g, n) in enumerate(zip(graphs, lens)):
+                seg[b, :len(g["blocks"])] = segment_table(g, state[b, :n])
+                cand[b, :len(g["blocks"])] = self.candidates(g)
+            arc = np.stack([np.log(self.loop), np.log(1.0 - self.loop)], 1) if self.transitions else np.zeros((self.n_classes, 2))
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)       # noqa: E731
+            V = segment_scores(x, lens, up(seg), up(cand).reshape(len(graphs), -1, P, S), *tables, up(arc)).cpu().numpy()
+            for b, g in enumerate(graphs):
+                nb = len(g["blocks"])
+                out[b]["V"] = V[b, :nb].copy()
+                out[b]["seg"], out[b]["gop_seg"] = segment_reductions(g, seg[b, :nb], out[b]["V"])
         return [frames[b, :len(g["blocks"])].copy() for b, g in enumerate(graphs)], out
 
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
-def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmllr_dim=0, transitions=0):
+def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmllr_dim=0, transitions=0, seg_phones=0, block_states=2):
     """`ragged.greedy_batches` of (frames, states) under `budget` bytes of device buffers: E, alpha / gamma and backpointers (17 B per
     cell), features, partials; with `mixtures` = M > 1 also the responsibilities (8 M B per cell) and M times the partials; with
     `splice_dim` = D_s > 0 (LDA) also the spliced frames, D_s doubles per frame, and their partials while the statistics are taken
     (the scatter workspace, at most 82 MB for any batch, is not counted); with `fmllr_dim` = D > 0 also the frame weights c, h and
     the adapted frames, 3 D doubles per frame (the accumulation workspace, at most 141 MB and 16 B per utterance, is not counted);
-    with `transitions` also the arc costs w and the second partial table xi, 3 + 5 doubles per state."""
+    with `transitions` also the arc costs w and the second partial table xi, 3 + 5 doubles per state; with `seg_phones` = P > 0
+    (segmental scores, `block_states` = S states per block) also, per block, the segment (8 B), its P S candidate classes (4 B
+    each) and its P values of V (8 B each)."""
     if mixtures == 1:
         base = lambda n, T, J: n * (T * J * 17 + T * dim * 8 + J * (1 + 2 * dim) * 8)       # noqa: E731
     else:
@@ -1897,6 +2075,9 @@ def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmll
     if transitions:
         plain_cost = cost
         cost = lambda n, T, J: plain_cost(n, T, J) + n * J * (3 + 5) * 8                  # noqa: E731
+    if seg_phones:
+        arcs_cost = cost
+        cost = lambda n, T, J: arcs_cost(n, T, J) + n * (J // block_states) * (8 + seg_phones * (4 * block_states + 8))  # noqa: E731
     return ragged.greedy_batches(list(zip(frames, states)), budget, cost)
 
 
@@ -1908,13 +2089,15 @@ def fmllr_dim_message(dim, lda):
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
           batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
           fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0,
-          questions=None, transitions=0, scores=None, g2p=None):
+          questions=None, transitions=0, scores=None, g2p=None, seg_scores=0):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason).  `scores` = a path: decoding goes through
     `Aligner.score` and one JSON object per written utterance goes to that file (the "Confidence" paragraph): speaker, basename,
     frames, scored_frames, viterbi, loglik, gop, match and phones = [label, start_s, end_s, loglik, gop, match] per written interval.
     `g2p` = a `fastspeech2_amd.g2p.G2P` model or the path of one: out-of-lexicon words get its pronunciation instead of `spn`
-    (`pronounce_oov`, one batched decode of the corpus's OOV words before any graph is built); the count is printed."""
+    (`pronounce_oov`, one batched decode of the corpus's OOV words before any graph is built); the count is printed.
+    `seg_scores` = 1 (needs `scores`): the "Segmental scores" paragraph; every phone entry becomes [label, start_s, end_s, loglik, gop,
+    match, gop_seg, rival_label, margin] and the utterance object gains gop_seg.  With 0 the scores file is what it was."""
     from . import audio as Audio
     from .preprocess import load_wav
     dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
@@ -1922,6 +2105,8 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
         raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
     if transitions not in (0, 1):
         raise ValueError(f"transitions must be 0 or 1, got {transitions}")
+    if seg_scores not in (0, 1) or (seg_scores and scores is None):
+        raise ValueError(f"seg_scores must be 0 or 1 and needs `scores`, got {seg_scores} with scores = {scores}")
     raw, out_dir = config["path"]["raw_path"], os.path.join(config["path"]["preprocessed_path"], "TextGrid")
     pp = config["preprocessing"]
     sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
@@ -1937,6 +2122,8 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     speaker_ids = {name: i for i, name in enumerate(speakers)}
     lexicon = read_lexicon(config["path"]["lexicon_path"])
     phone_ids = phone_table(lexicon)
+    if seg_scores and len(phone_ids) > max_seg_phones():
+        raise ValueError(f"seg_scores takes at most {max_seg_phones()} phones, the lexicon has {len(phone_ids)}")
     if triphones:
         if not float(tri_min_occ) >= 1.0:
             raise ValueError(f"tri_min_occ must be at least 1, got {tri_min_occ}")
@@ -2022,7 +2209,7 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     frames, nstates = [it["x"].shape[0] for it in items], [len(it["graph"]["sid"]) for it in items]
     resident = sum(frames) * D * 8 <= resident_bytes
     packed = []
-    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures, Ds, Df, transitions):
+    for batch in batches_by_bytes(frames, nstates, D, batch_bytes, mixtures, Ds, Df, transitions, len(phone_ids) if seg_scores else 0, states):
         feats = torch.zeros(len(batch), max(frames[i] for i in batch), D, dtype=torch.float64)
         for r, i in enumerate(batch):
             feats[r, :frames[i]] = items[i]["x"]
@@ -2037,13 +2224,15 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     history = aligner.fit([p[:3] for p in packed], iters, [spk_of(p[3]) for p in packed] if fmllr else None)
 
     written = 0
+    phone_names = sorted(phone_ids, key=phone_ids.get)
+    none_if_nan = lambda v: None if v != v else float(v)                                 # noqa: E731
     sink = open(scores, "w", encoding="utf-8") if scores is not None else None
     try:
         for feats, lens, graphs, batch in packed:
             if sink is None:
                 got, conf = aligner.align(feats, lens, graphs, spk_of(batch)), [None] * len(batch)
             else:
-                got, conf = aligner.score(feats, lens, graphs, spk_of(batch))
+                got, conf = aligner.score(feats, lens, graphs, spk_of(batch), segmental=bool(seg_scores))
             for i, fr, sc in zip(batch, got, conf):
                 e = items[i]["entry"]
                 os.makedirs(os.path.join(out_dir, e[0]), exist_ok=True)
@@ -2054,6 +2243,10 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
                     rows = sc["blocks"][np.nonzero(fr)[0]]                 # the written intervals: the blocks with frames
                     line = {"speaker": e[0], "basename": e[1], **{k: sc[k] for k in ("frames", "scored_frames", "viterbi", "loglik", "gop", "match")},
                             "phones": [[p, s0, s1] + [float(v) for v in r] for (s0, s1, p), r in zip(ph, rows)]}
+                    if seg_scores:
+                        line["gop_seg"] = none_if_nan(sc["gop_seg"])
+                        for entry, (g_, q, m) in zip(line["phones"], sc["seg"][np.nonzero(fr)[0]]):
+                            entry += [none_if_nan(g_), None if q != q else phone_names[int(q)], none_if_nan(m)]
                     sink.write(json.dumps(line, allow_nan=False) + "\n")
     finally:
         if sink is not None:

@@ -508,6 +508,26 @@ int fs2_align_frame_scores(const double* f, long ldf_b, long ldf_t, const int32_
                            const double* w, const double* mu, const double* var, int n_classes, int M, int D, double* ws,
                            long ws_doubles, double* own, long ldo_b, double* best, long ldb_b, int32_t* arg, long lda_b, int B,
                            int Tmax, fs2_stream_t stream);
+/* Segmental scores (csrc/fs2_align_seg.hip; specification: the "Segmental scores" paragraph of fastspeech2_amd/align.py).  No atomics.
+ * The largest number of candidate phones P (256), and the doubles of workspace fs2_align_segment_scores needs: n_classes M (D + 1)
+ * (0 for tables outside the limits of fs2_align_frame_scores). */
+int fs2_align_max_seg_phones(void);
+int fs2_align_segment_scores_ws(int n_classes, int M, int D);
+/* For every block k < Kmax of every utterance: seg[b][k] = (start, frames) (int32, batch stride lds_b >= 2 Kmax) is a run of frames
+ * of f (as for fs2_align_frame_scores), cand[b][k][q S + s] (int32, strides ldc_b >= Kmax ldc_k, ldc_k >= P S) the class of state s
+ * of candidate phone q < P, arc[c] = (ws, wn) the log-probabilities of staying in and of leaving class c ([n_classes][2]).  With
+ * F[t][c] of fs2_align_frame_scores (the same preparation into ws, the same statements per frame, class and component):
+ * v_0(start) = F[start][c_0], v_s(start) = -inf for s > 0; v_s(t) = F[t][c_s] + max(v_s(t-1) + ws[c_s], v_{s-1}(t-1) + wn[c_{s-1}]);
+ * V[b][k][q] = v_{S-1}(start + frames - 1) + wn[c_{S-1}], -inf when frames < S (double, strides ldv_b >= Kmax ldv_k, ldv_k >= P).
+ * Two phones with identical table rows get identical bits.  A block with frames <= 0, start < 0, start + frames > lens[b] or a
+ * negative entry among its P S candidates is absent: its V row is not written and nothing is read for it.  A candidate class
+ * >= n_classes scores -inf and the tables are not read for it.  FS2_EINVAL before any launch: P outside
+ * 1..fs2_align_max_seg_phones(), S outside 1..3, M outside 1..fs2_align_max_mixtures(), D <= 0, n_classes <= 0, n_classes M (D + 1) >=
+ * 2^31, B > 65535, a bad stride, a null pointer, ws_doubles below fs2_align_segment_scores_ws(). */
+int fs2_align_segment_scores(const double* f, long ldf_b, long ldf_t, const int32_t* lens, const int32_t* seg, long lds_b,
+                             const int32_t* cand, long ldc_b, long ldc_k, const double* w, const double* mu, const double* var,
+                             int n_classes, int M, int D, const double* arc, double* ws, long ws_doubles, double* V, long ldv_b,
+                             long ldv_k, int B, int Tmax, int Kmax, int P, int S, fs2_stream_t stream);
 /* The LDA stage (csrc/fs2_align_lda.hip).  Spliced frames y [B][Tmax][D_s], D_s = n_mel (2 c + 1), strides ldy_b >= Tmax ldy_t,
  * ldy_t >= D_s, in elements.  Limits, all FS2_EINVAL before any launch: 0 <= c <= 4, 1 <= k <= D_s <= fs2_align_max_splice_dim() (720).
  * Nothing at t >= lens[b] is read or written.  No atomics. */
