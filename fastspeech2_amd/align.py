@@ -328,6 +328,23 @@ TRANS_FLOOR = 0.01
 _SPLIT = re.compile(r"[,;.\-\?\!\s+]")
 
 
+def _up(a, device):
+    """A numpy array on the device."""
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def _csr(classes, n, device, rows=None):
+    """CSR (class -> the rows of that class, in their given order) of a class vector over n classes: (offs (n + 1,), items) int32
+    on the device.  `rows` names the row of every entry (default: its position).  Never an empty item tensor: the lists bound
+    what is read."""
+    classes = np.asarray(classes, np.int64)
+    order = np.argsort(classes, kind="stable")
+    offs = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(classes, minlength=n), out=offs[1:])
+    items = order if rows is None else np.asarray(rows, np.int64)[order]
+    return _up(offs.astype(np.int32), device), _up((items if items.size else np.zeros(1)).astype(np.int32), device)
+
+
 # ------------------------------------------------------------------------------------------------ lexicon, text, graph
 def read_lexicon(path):
     lexicon = {}
@@ -539,6 +556,18 @@ def _dev(t, dtype, what, dim=3):
     return t
 
 
+def _out(out, shape, device, least=(1,), alloc=None, what="out", dtype=torch.float64):
+    """The `out=` of a wrapper: a fresh buffer of shape `alloc` (default `shape`), or `out` checked against `shape`, where the
+    dimensions listed in `least` may be larger."""
+    if out is None:
+        return torch.empty(alloc or tuple(shape), dtype=dtype, device=device)
+    out = _dev(out, dtype, what, len(shape))
+    if any(got < n if d in least else got != n for d, (got, n) in enumerate(zip(out.shape, shape))):
+        want = ", ".join(f">= {n}" if d in least else str(n) for d, n in enumerate(shape))
+        raise ValueError(f"{what} {tuple(out.shape)} is not ({want})")
+    return out
+
+
 class Graphs:
     """The graphs of one ragged batch on the device: sid / skip / block [B][Jmax] int32 (-1 padded), alt [B][2], jlens."""
 
@@ -553,8 +582,7 @@ class Graphs:
         for b, g in enumerate(graphs):
             for i, k in enumerate(("sid", "skip", "block")):
                 packed[i, b, :self.jl[b]] = g[k]
-        d = torch.from_numpy(packed).to(device)
-        self.sid, self.skip, self.block = d[0], d[1], d[2]
+        self.sid, self.skip, self.block = _up(packed, device)
         self.alt = torch.tensor([g["alt"] for g in graphs], dtype=torch.int32, device=device).reshape(-1, 2)
         self.jlens = torch.tensor(self.jl, dtype=torch.int32, device=device)
         self.ldg = max(self.Jmax, 1)
@@ -566,8 +594,7 @@ class Graphs:
         w, edge = np.zeros((len(self.graphs), 3, self.ldg)), np.zeros((len(self.graphs), 4))
         for b, g in enumerate(self.graphs):
             w[b, :, :self.jl[b]], edge[b] = arc_costs(g, loop, opt)
-        dev = self.sid.device
-        self.w, self.edge = torch.from_numpy(w).to(dev), torch.from_numpy(edge).to(dev)
+        self.w, self.edge = _up(w, self.sid.device), _up(edge, self.sid.device)
 
     def arc_index(self, n_classes):
         """The two CSR lists that reduce the arc posteriors xi (B, ldg, 5): the class list of `index` and the list of the optional
@@ -584,12 +611,8 @@ class Graphs:
                         rows[2].append(at + first[k]), rows[3].append(at + first[k + 1])
                     elif kind == 2:
                         rows[4].append(at + first[k]), rows[5].append(at + g["alt"][1])
-            offs = np.zeros(7, np.int64)
-            np.cumsum([len(r) for r in rows], out=offs[1:])
-            items = np.array([i for r in rows for i in r] or [0], np.int64)    # never an empty tensor: the lists bound what is read
-            dev = self.sid.device
-            self._arc_index[n_classes] = (self.index(n_classes, self.ldg),
-                                          (torch.from_numpy(offs.astype(np.int32)).to(dev), torch.from_numpy(items.astype(np.int32)).to(dev)))
+            kinds = _csr(np.repeat(np.arange(6), [len(r) for r in rows]), 6, self.sid.device, [i for r in rows for i in r])
+            self._arc_index[n_classes] = (self.index(n_classes, self.ldg), kinds)
         return self._arc_index[n_classes]
 
     def index(self, n_classes, ld_j, mixtures=1):
@@ -604,11 +627,7 @@ class Graphs:
             comp = np.arange(mixtures, dtype=np.int64)[None, :]
             cls, rows = (cls[:, None] * mixtures + comp).ravel(), (rows[:, None] * mixtures + comp).ravel()
             n_classes *= mixtures
-        order = np.argsort(cls, kind="stable")
-        offs = np.zeros(n_classes + 1, np.int64)
-        np.cumsum(np.bincount(cls, minlength=n_classes), out=offs[1:])
-        dev = self.sid.device
-        return torch.from_numpy(offs.astype(np.int32)).to(dev), torch.from_numpy(rows[order].astype(np.int32)).to(dev)
+        return _csr(cls, n_classes, self.sid.device, rows)
 
 
 def _check_scan(E, lens, G):
@@ -641,9 +660,7 @@ def emit(x, lens, G, mu, var, out=None):
     if mu.shape != var.shape or mu.shape[1] != D or B != len(G.jl):
         raise ValueError(f"x {tuple(x.shape)}, mu {tuple(mu.shape)}, var {tuple(var.shape)}, {len(G.jl)} graphs do not fit together")
     _, lens_d = ragged.lengths(lens, B, Tmax, "lens", x.device)
-    E = torch.empty(B, Tmax, G.Jmax, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
-    if E.shape[0] != B or E.shape[1] < Tmax or E.shape[2] < G.Jmax:
-        raise ValueError(f"out {tuple(E.shape)} is too small for ({B}, {Tmax}, {G.Jmax})")
+    E = _out(out, (B, Tmax, G.Jmax), x.device, least=(1, 2))
     _lib.call("fs2_align_emit", x.data_ptr(), x.stride(0), x.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.sid.data_ptr(), G.ldg,
               mu.data_ptr(), var.data_ptr(), mu.shape[0], D, E.data_ptr(), E.stride(0), E.stride(1), B, Tmax, G.Jmax, ops._stream())
     return E
@@ -676,9 +693,7 @@ def emit_gmm(x, lens, G, w, mu, var, out=None, resp=None):
     if B != len(G.jl):
         raise ValueError(f"x {tuple(x.shape)} and {len(G.jl)} graphs do not fit together")
     _, lens_d = ragged.lengths(lens, B, Tmax, "lens", x.device)
-    E = torch.empty(B, Tmax, G.Jmax, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
-    if E.shape[0] != B or E.shape[1] < Tmax or E.shape[2] < G.Jmax:
-        raise ValueError(f"out {tuple(E.shape)} is too small for ({B}, {Tmax}, {G.Jmax})")
+    E = _out(out, (B, Tmax, G.Jmax), x.device, least=(1, 2))
     rp, rs = None, (0, 0, 0)
     if resp is not None:
         resp = _dev(resp, torch.float64, "resp", 4)
@@ -691,75 +706,63 @@ def emit_gmm(x, lens, G, w, mu, var, out=None, resp=None):
     return E
 
 
-def forward(E, lens, G, out=None):
-    """-> (alpha like E, loglik (B,)) on the device."""
-    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
-    alpha = torch.empty_like(E) if out is None else _dev(out, torch.float64, "out")
-    if alpha.shape != E.shape:
-        raise ValueError("out must have E's shape")
-    loglik = torch.empty(B, dtype=torch.float64, device=E.device)
-    _lib.call("fs2_align_forward", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.skip.data_ptr(),
-              G.ldg, G.alt.data_ptr(), alpha.data_ptr(), alpha.stride(0), alpha.stride(1), loglik.data_ptr(), B, Tmax, G.Jmax,
-              ops._stream())
-    return alpha, loglik
-
-
-def backward(E, lens, G, alpha, loglik, out=None):
-    """gamma = exp(alpha + beta - loglik), written over alpha unless `out` is given."""
-    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
-    alpha = _dev(alpha, torch.float64, "alpha")
-    gamma = alpha if out is None else _dev(out, torch.float64, "out")
-    loglik = _dev(loglik, torch.float64, "loglik", 1)
-    if alpha.shape != E.shape or gamma.shape != E.shape or loglik.shape[0] != B:
-        raise ValueError("alpha and out must have E's shape, loglik B values")
-    _lib.call("fs2_align_backward", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.skip.data_ptr(),
-              G.ldg, G.alt.data_ptr(), alpha.data_ptr(), alpha.stride(0), alpha.stride(1), loglik.data_ptr(), gamma.data_ptr(),
-              gamma.stride(0), gamma.stride(1), B, Tmax, G.Jmax, ops._stream())
-    return gamma
-
-
-def _check_arcs(w, edge, B, G):
+def _arc_args(w, edge, B, G):
+    """The suffix of a scan's entry point and the arguments it takes more under the arc costs w (B, 3, >= Jmax) and edge (B, 4):
+    ("", ()) without costs, else ("_arcs", (w, its row stride, edge)) after the checks."""
+    if w is None and edge is None:
+        return "", ()
+    if w is None or edge is None:
+        raise ValueError("w and edge are given together or not at all")
     _no_host(w=w, edge=edge)
     w, edge = _dev(w, torch.float64, "w"), _dev(edge, torch.float64, "edge", 2)
     if w.shape[0] != B or w.shape[1] != 3 or w.shape[2] < G.Jmax or (B and w.stride(0) != 3 * w.stride(1)) or \
             tuple(edge.shape) != (B, 4) or not edge.is_contiguous():
         raise ValueError(f"w {tuple(w.shape)} (strides {w.stride()}) and edge {tuple(edge.shape)} are not the arc costs [B][3][ldw] and "
                          f"[B][4] of {B} utterances of up to {G.Jmax} states")
-    return w, edge
+    return "_arcs", (w.data_ptr(), w.stride(1), edge.data_ptr())
 
 
-def forward_arcs(E, lens, G, w, edge, out=None):
-    """`forward` under the arc costs w (B, 3, >= Jmax) and edge (B, 4) -> (alpha like E, loglik (B,)) on the device."""
+def forward(E, lens, G, out=None, w=None, edge=None):
+    """-> (alpha like E, loglik (B,)) on the device; under the arc costs w, edge when they are given."""
     E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
-    w, edge = _check_arcs(w, edge, B, G)
-    alpha = torch.empty_like(E) if out is None else _dev(out, torch.float64, "out")
-    if alpha.shape != E.shape:
-        raise ValueError("out must have E's shape")
+    arcs, costs = _arc_args(w, edge, B, G)
+    alpha = _out(out, E.shape, E.device, least=())
     loglik = torch.empty(B, dtype=torch.float64, device=E.device)
-    _lib.call("fs2_align_forward_arcs", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
-              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), w.data_ptr(), w.stride(1), edge.data_ptr(), alpha.data_ptr(), alpha.stride(0),
-              alpha.stride(1), loglik.data_ptr(), B, Tmax, G.Jmax, ops._stream())
+    _lib.call("fs2_align_forward" + arcs, E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), *costs, alpha.data_ptr(), alpha.stride(0), alpha.stride(1), loglik.data_ptr(),
+              B, Tmax, G.Jmax, ops._stream())
     return alpha, loglik
 
 
-def backward_arcs(E, lens, G, w, edge, alpha, loglik, out=None, xi=None):
-    """`backward` under the arc costs -> (gamma, written over alpha unless `out` is given; xi (B, >= Jmax, 5): the arc posteriors
-    self, next, skip of every state, then its start mass gamma[0, j] and its end mass gamma[T - 1, j])."""
+def backward(E, lens, G, alpha, loglik, out=None, w=None, edge=None, xi=None):
+    """gamma = exp(alpha + beta - loglik), written over alpha unless `out` is given.  Under the arc costs w, edge -> (gamma, xi
+    (B, >= Jmax, 5): the arc posteriors self, next, skip of every state, then its start mass gamma[0, j] and its end mass
+    gamma[T - 1, j])."""
     E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
-    w, edge = _check_arcs(w, edge, B, G)
+    arcs, costs = _arc_args(w, edge, B, G)
     alpha = _dev(alpha, torch.float64, "alpha")
     gamma = alpha if out is None else _dev(out, torch.float64, "out")
     loglik = _dev(loglik, torch.float64, "loglik", 1)
     if alpha.shape != E.shape or gamma.shape != E.shape or loglik.shape[0] != B:
         raise ValueError("alpha and out must have E's shape, loglik B values")
-    xi = torch.empty(B, G.ldg, 5, dtype=torch.float64, device=E.device) if xi is None else _dev(xi, torch.float64, "xi")
-    if xi.shape[0] != B or xi.shape[1] < G.Jmax or xi.shape[2] != 5:
-        raise ValueError(f"xi {tuple(xi.shape)} is not ({B}, >= {G.Jmax}, 5)")
-    _lib.call("fs2_align_backward_arcs", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
-              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), w.data_ptr(), w.stride(1), edge.data_ptr(), alpha.data_ptr(), alpha.stride(0),
-              alpha.stride(1), loglik.data_ptr(), gamma.data_ptr(), gamma.stride(0), gamma.stride(1), xi.data_ptr(), xi.stride(0),
-              xi.stride(1), B, Tmax, G.Jmax, ops._stream())
-    return gamma, xi
+    sums = ()
+    if arcs:
+        xi = _out(xi, (B, G.Jmax, 5), E.device, alloc=(B, G.ldg, 5), what="xi")
+        sums = (xi.data_ptr(), xi.stride(0), xi.stride(1))
+    _lib.call("fs2_align_backward" + arcs, E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), *costs, alpha.data_ptr(), alpha.stride(0), alpha.stride(1), loglik.data_ptr(),
+              gamma.data_ptr(), gamma.stride(0), gamma.stride(1), *sums, B, Tmax, G.Jmax, ops._stream())
+    return (gamma, xi) if arcs else gamma
+
+
+def forward_arcs(E, lens, G, w, edge, out=None):
+    """`forward` under the arc costs w (B, 3, >= Jmax) and edge (B, 4)."""
+    return forward(E, lens, G, out, w, edge)
+
+
+def backward_arcs(E, lens, G, w, edge, alpha, loglik, out=None, xi=None):
+    """`backward` under the arc costs -> (gamma, xi)."""
+    return backward(E, lens, G, alpha, loglik, out, w, edge, xi)
 
 
 def stats(gamma, x, lens, G, out=None):
@@ -769,9 +772,7 @@ def stats(gamma, x, lens, G, out=None):
     D = x.shape[2]
     if x.shape[0] != B or x.shape[1] < Tmax:
         raise ValueError(f"x {tuple(x.shape)} does not cover gamma {tuple(gamma.shape)}")
-    P = torch.empty(B, G.ldg, 1 + 2 * D, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
-    if P.shape[0] != B or P.shape[1] < G.Jmax or P.shape[2] != 1 + 2 * D:
-        raise ValueError(f"out {tuple(P.shape)} is not ({B}, >= {G.Jmax}, {1 + 2 * D})")
+    P = _out(out, (B, G.Jmax, 1 + 2 * D), x.device, alloc=(B, G.ldg, 1 + 2 * D))
     _lib.call("fs2_align_stats", gamma.data_ptr(), gamma.stride(0), gamma.stride(1), x.data_ptr(), x.stride(0), x.stride(1),
               lens_d.data_ptr(), G.jlens.data_ptr(), D, P.data_ptr(), P.stride(0), P.stride(1), B, Tmax, G.Jmax, ops._stream())
     return P
@@ -847,9 +848,7 @@ def splice(x, lens, n_mel, context, out=None):
     if D < n_mel:
         raise ValueError(f"x {tuple(x.shape)} has fewer than {n_mel} columns")
     _, lens_d = ragged.lengths(lens, B, Tmax, "lens", x.device)
-    y = torch.empty(B, Tmax, Ds, dtype=torch.float64, device=x.device) if out is None else _dev(out, torch.float64, "out")
-    if y.shape[0] != B or y.shape[1] < Tmax or y.shape[2] != Ds:
-        raise ValueError(f"out {tuple(y.shape)} is not ({B}, >= {Tmax}, {Ds})")
+    y = _out(out, (B, Tmax, Ds), x.device)
     _lib.call("fs2_align_splice", x.data_ptr(), x.stride(0), x.stride(1), lens_d.data_ptr(), int(n_mel), int(context), y.data_ptr(),
               y.stride(0), y.stride(1), B, Tmax, ops._stream())
     return y
@@ -891,9 +890,7 @@ def project(y, lens, P, o, out=None):
     if not 1 <= k <= Ds <= max_splice_dim():
         raise ValueError(f"{k} outputs of {Ds} dimensions, supported are 1 <= k <= D_s <= {max_splice_dim()}")
     _, lens_d = ragged.lengths(lens, B, Tmax, "lens", y.device)
-    z = torch.empty(B, Tmax, k, dtype=torch.float64, device=y.device) if out is None else _dev(out, torch.float64, "out")
-    if z.shape[0] != B or z.shape[1] < Tmax or z.shape[2] != k:
-        raise ValueError(f"out {tuple(z.shape)} is not ({B}, >= {Tmax}, {k})")
+    z = _out(out, (B, Tmax, k), y.device)
     _lib.call("fs2_align_project", y.data_ptr(), y.stride(0), y.stride(1), lens_d.data_ptr(), P.data_ptr(), o.data_ptr(), k, Ds,
               z.data_ptr(), z.stride(0), z.stride(1), B, Tmax, ops._stream())
     return z
@@ -994,11 +991,7 @@ def fmllr_accumulate(f, c, h, lens, speakers, n_spk, beta=None, G=None, k=None):
         raise ValueError(f"beta {tuple(beta.shape)}, G {tuple(G.shape)}, k {tuple(k.shape)} are not the contiguous tables of {n_spk} "
                          f"speakers in {D} dimensions")
     _, lens_d = ragged.lengths(lens, B, Tmax, "lens", f.device)
-    offs = np.zeros(n_spk + 1, np.int64)                                   # CSR speaker -> batch rows, in batch-row order
-    np.cumsum(np.bincount(sp, minlength=n_spk), out=offs[1:])
-    rows = np.argsort(sp, kind="stable")
-    offs_d = torch.from_numpy(offs.astype(np.int32)).to(f.device)
-    rows_d = torch.from_numpy(rows.astype(np.int32)).to(f.device)
+    offs_d, rows_d = _csr(sp, n_spk, f.device)                             # speaker -> batch rows, in batch-row order
     n_ws = _lib.load().fs2_align_fmllr_accum_ws(B, Tmax, D)
     ws = torch.empty(max(n_ws, 1), dtype=torch.float64, device=f.device)
     _lib.call("fs2_align_fmllr_accum", f.data_ptr(), f.stride(0), f.stride(1), c.data_ptr(), h.data_ptr(), c.stride(0), c.stride(1),
@@ -1017,10 +1010,8 @@ def fmllr_apply(f, lens, W, speakers, out=None):
         raise ValueError(f"W {tuple(W.shape)} is not (n_spk, {D}, {D + 1})")
     sp = _speaker_list(speakers, B, W.shape[0])
     _, lens_d = ragged.lengths(lens, B, Tmax, "lens", f.device)
-    fh = torch.empty(B, Tmax, D, dtype=torch.float64, device=f.device) if out is None else _dev(out, torch.float64, "out")
-    if fh.shape[0] != B or fh.shape[1] < Tmax or fh.shape[2] != D:
-        raise ValueError(f"out {tuple(fh.shape)} is not ({B}, >= {Tmax}, {D})")
-    spk_d = torch.from_numpy(sp.astype(np.int32)).to(f.device)
+    fh = _out(out, (B, Tmax, D), f.device)
+    spk_d = _up(sp.astype(np.int32), f.device)
     _lib.call("fs2_align_fmllr_apply", f.data_ptr(), f.stride(0), f.stride(1), lens_d.data_ptr(), W.data_ptr(), spk_d.data_ptr(),
               W.shape[0], D, fh.data_ptr(), fh.stride(0), fh.stride(1), B, Tmax, ops._stream())
     return fh
@@ -1217,13 +1208,18 @@ def tree_build(keys, roots, n_roots, fixed, member, gains_of, min_gain=0.0):
     return t
 
 
+def check_leaves(budget, n_roots):
+    """The leaf budget `triphones` against the roots of the tree, one per monophone state (fixed leaves included)."""
+    if budget < n_roots:
+        raise ValueError(f"triphones = {budget} leaves is below the {n_roots} roots and fixed leaves")
+
+
 def tree_replay(tree, n_roots, budget):
     """The leaf budget: the recorded splits replayed through a priority queue, the largest gain first, the lowest node number on ties,
     until `budget` leaves exist or no split is left -> (question, yes, no, leaf: int32 arrays over the nodes of the full tree, -1
     where a node was not split / is no leaf of the pruned tree; the total gain of the splits kept)."""
     import heapq
-    if budget < n_roots:
-        raise ValueError(f"triphones = {budget} leaves is below the {n_roots} roots and fixed leaves")
+    check_leaves(budget, n_roots)
     n = len(tree["question"])
     heap = [(-tree["gain"][m], m) for m in range(n_roots) if tree["question"][m] >= 0]
     heapq.heapify(heap)
@@ -1259,33 +1255,23 @@ def tree_leaves(question, yes, no, leaf, member, keys, states):
         node = np.where(go, np.where(ans, yes[node], no[node]), node)
 
 
-def viterbi(E, lens, G, out=None):
-    """-> (backpointers uint8 like E, best end state (B,) int32, its score (B,) float64)."""
+def viterbi(E, lens, G, out=None, w=None, edge=None):
+    """-> (backpointers uint8 like E, best end state (B,) int32, its score (B,) float64); under the arc costs w, edge when they are
+    given, and the score then includes the end edge."""
     E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
-    bp = torch.empty(E.shape, dtype=torch.uint8, device=E.device) if out is None else _dev(out, torch.uint8, "out")
-    if bp.shape != E.shape:
-        raise ValueError("out must have E's shape")
+    arcs, costs = _arc_args(w, edge, B, G)
+    bp = _out(out, E.shape, E.device, least=(), dtype=torch.uint8)
     end = torch.empty(B, dtype=torch.int32, device=E.device)
     score = torch.empty(B, dtype=torch.float64, device=E.device)
-    _lib.call("fs2_align_viterbi", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(), G.skip.data_ptr(),
-              G.ldg, G.alt.data_ptr(), bp.data_ptr(), bp.stride(0), bp.stride(1), end.data_ptr(), score.data_ptr(), B, Tmax, G.Jmax,
-              ops._stream())
+    _lib.call("fs2_align_viterbi" + arcs, E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
+              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), *costs, bp.data_ptr(), bp.stride(0), bp.stride(1), end.data_ptr(),
+              score.data_ptr(), B, Tmax, G.Jmax, ops._stream())
     return bp, end, score
 
 
 def viterbi_arcs(E, lens, G, w, edge, out=None):
-    """`viterbi` under the arc costs; the score includes the end edge."""
-    E, B, Tmax, _, lens_d = _check_scan(E, lens, G)
-    w, edge = _check_arcs(w, edge, B, G)
-    bp = torch.empty(E.shape, dtype=torch.uint8, device=E.device) if out is None else _dev(out, torch.uint8, "out")
-    if bp.shape != E.shape:
-        raise ValueError("out must have E's shape")
-    end = torch.empty(B, dtype=torch.int32, device=E.device)
-    score = torch.empty(B, dtype=torch.float64, device=E.device)
-    _lib.call("fs2_align_viterbi_arcs", E.data_ptr(), E.stride(0), E.stride(1), lens_d.data_ptr(), G.jlens.data_ptr(),
-              G.skip.data_ptr(), G.ldg, G.alt.data_ptr(), w.data_ptr(), w.stride(1), edge.data_ptr(), bp.data_ptr(), bp.stride(0),
-              bp.stride(1), end.data_ptr(), score.data_ptr(), B, Tmax, G.Jmax, ops._stream())
-    return bp, end, score
+    """`viterbi` under the arc costs w (B, 3, >= Jmax) and edge (B, 4)."""
+    return viterbi(E, lens, G, out, w, edge)
 
 
 def backtrack(bp, lens, G, end):
@@ -1498,6 +1484,46 @@ def segment_reductions(graph, seg, V):
 
 
 # ------------------------------------------------------------------------------------------------ the model
+def fmllr_dim_message(dim, lda):
+    return (f"fmllr adapts at most {max_fmllr_dim()} feature dimensions (a speaker's statistics are D (D + 1)(D + 2) doubles), got {dim}"
+            + ("" if lda else f": with {dim // 2} mel channels --fmllr needs --lda k with k <= {max_fmllr_dim()}"))
+
+
+def check_options(dim, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2, fmllr_iters=2, fmllr_sweeps=20,
+                  fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0, transitions=0):
+    """The stage switches of `Aligner` and `build` for features of `dim` = 2 n_mel columns; a bad one is a ValueError before any
+    work -> (n_mel, D_s of the LDA or 0, the dimension the Gaussian stages after the LDA see)."""
+    n_mel, Ds = dim // 2, 0
+    if int(transitions) not in (0, 1):
+        raise ValueError(f"transitions must be 0 or 1, got {transitions}")
+    if int(lda) != 0:
+        if dim % 2:
+            raise ValueError(f"dim {dim} is not 2 n_mel")
+        Ds = splice_dim(n_mel, int(splice), int(lda))
+        if int(lda_iters) < 0:
+            raise ValueError(f"lda_iters must not be negative, got {lda_iters}")
+        dim = int(lda)
+    if int(fmllr) != 0:
+        if int(fmllr) != 1:
+            raise ValueError(f"fmllr must be 0 or 1, got {fmllr}")
+        if not 1 <= dim <= max_fmllr_dim():
+            raise ValueError(fmllr_dim_message(dim, int(lda)))
+        if int(fmllr_rounds) < 1 or int(fmllr_iters) < 0 or int(fmllr_sweeps) < 1 or float(fmllr_min_frames) < 0:
+            raise ValueError(f"fmllr_rounds {fmllr_rounds} and fmllr_sweeps {fmllr_sweeps} must be at least 1, fmllr_iters "
+                             f"{fmllr_iters} and fmllr_min_frames {fmllr_min_frames} not negative")
+    if int(triphones) != 0:
+        if not float(tri_min_occ) >= 1.0:
+            raise ValueError(f"tri_min_occ must be at least 1, got {tri_min_occ}")
+        if int(tri_iters) < 0 or not float(tri_min_gain) >= 0.0:
+            raise ValueError(f"tri_iters {tri_iters} and tri_min_gain {tri_min_gain} must not be negative")
+    if int(mixtures) != 1:
+        if not 1 <= int(mixtures) <= max_mixtures():
+            raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
+        if int(mix_iters) < 1:
+            raise ValueError(f"mix_iters must be at least 1, got {mix_iters}")
+    return n_mel, Ds, dim
+
+
 class Aligner:
     """The class table (mu, var: (n_classes, dim) float64) on the device, trained by `fit`, used by `align`.  With `mixtures` = M > 1
     `fit` goes on from that table to the mixture tables gw (n_classes, M), gmu, gvar (n_classes, M, dim) on the device and ncomp
@@ -1520,55 +1546,35 @@ class Aligner:
         self.mu = torch.zeros(n_classes, dim, dtype=torch.float64, device=self.device)
         self.var = torch.ones(n_classes, dim, dtype=torch.float64, device=self.device)
         self.floor = np.zeros(dim)
+        self.n_mel, self.splice_dim, dim = check_options(                  # the tables after the LDA live in z: dim = lda
+            dim, mixtures, mix_iters, lda, splice, lda_iters, fmllr, fmllr_rounds, fmllr_iters, fmllr_sweeps, fmllr_min_frames, triphones,
+            tri_iters, tri_min_occ, tri_min_gain, transitions)
         self.transitions = int(transitions)
-        if self.transitions not in (0, 1):
-            raise ValueError(f"transitions must be 0 or 1, got {transitions}")
         self.loop, self.opt = np.full(n_classes, 0.5), np.full(3, 0.5)
         self.mixtures, self.mix_iters, self.min_split_occ = int(mixtures), int(mix_iters), float(min_split_occ)
         self.lda, self.splice, self.lda_iters, self.P, self.o = int(lda), int(splice), int(lda_iters), None, None
-        if self.lda != 0:
-            if dim % 2:
-                raise ValueError(f"dim {dim} is not 2 n_mel")
-            self.n_mel = dim // 2
-            self.splice_dim = splice_dim(self.n_mel, self.splice, self.lda)
-            if self.lda_iters < 0:
-                raise ValueError(f"lda_iters must not be negative, got {lda_iters}")
-            dim = self.lda                                                 # the mixture tables live in z
         self.fmllr, self.W, self.n_spk = int(fmllr), None, 0
         self.fmllr_rounds, self.fmllr_iters, self.fmllr_sweeps = int(fmllr_rounds), int(fmllr_iters), int(fmllr_sweeps)
         self.fmllr_min_frames = float(fmllr_min_frames)
-        if self.fmllr != 0:
-            if self.fmllr != 1:
-                raise ValueError(f"fmllr must be 0 or 1, got {fmllr}")
-            if not 1 <= dim <= max_fmllr_dim():
-                raise ValueError(fmllr_dim_message(dim, self.lda))
-            if self.fmllr_rounds < 1 or self.fmllr_iters < 0 or self.fmllr_sweeps < 1 or self.fmllr_min_frames < 0:
-                raise ValueError(f"fmllr_rounds {fmllr_rounds} and fmllr_sweeps {fmllr_sweeps} must be at least 1, fmllr_iters "
-                                 f"{fmllr_iters} and fmllr_min_frames {fmllr_min_frames} not negative")
         self.triphones, self.tri_iters, self.tri_min_occ, self.tri_min_gain = int(triphones), int(tri_iters), float(tri_min_occ), float(tri_min_gain)
         self.questions, self.phone_ids, self.tree = questions, phone_ids, None
         if self.triphones != 0:
             if phone_ids is None or len(phone_ids) * states != n_classes or any(p not in phone_ids for p in (SIL, SP, SPN)):
                 raise ValueError(f"an Aligner with triphones needs `phone_ids`, the phone table of its {n_classes // states} phones")
-            if self.triphones < n_classes:
-                raise ValueError(f"triphones = {triphones} leaves is below the {n_classes} roots and fixed leaves")
-            if not self.tri_min_occ >= 1.0:
-                raise ValueError(f"tri_min_occ must be at least 1, got {tri_min_occ}")
-            if self.tri_iters < 0 or not self.tri_min_gain >= 0.0:
-                raise ValueError(f"tri_iters {tri_iters} and tri_min_gain {tri_min_gain} must not be negative")
+            check_leaves(triphones, n_classes)
             self.question_sets = read_questions(questions, phone_ids) if questions is not None else None
             if self.question_sets is not None and len(self.question_sets[0]) > max_tree_sets():
                 raise ValueError(f"{len(self.question_sets[0])} question sets, supported are 1..{max_tree_sets()}")
         if self.mixtures != 1:
-            if not 1 <= self.mixtures <= max_mixtures():
-                raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
-            if self.mix_iters < 1:
-                raise ValueError(f"mix_iters must be at least 1, got {mix_iters}")
-            self.gw = torch.zeros(n_classes, self.mixtures, dtype=torch.float64, device=self.device)
-            self.gw[:, 0] = 1.0
-            self.gmu = torch.zeros(n_classes, self.mixtures, dim, dtype=torch.float64, device=self.device)
-            self.gvar = torch.ones(n_classes, self.mixtures, dim, dtype=torch.float64, device=self.device)
-            self.ncomp = np.ones(n_classes, np.int64)
+            self._mixture_tables(n_classes, dim)
+
+    def _mixture_tables(self, C, dim):
+        """Fresh mixture tables for C classes: every class one active component of weight 1."""
+        self.gw = torch.zeros(C, self.mixtures, dtype=torch.float64, device=self.device)
+        self.gw[:, 0] = 1.0
+        self.gmu = torch.zeros(C, self.mixtures, dim, dtype=torch.float64, device=self.device)
+        self.gvar = torch.ones(C, self.mixtures, dim, dtype=torch.float64, device=self.device)
+        self.ncomp = np.ones(C, np.int64)
 
     def _prepare(self, feats, lens, graphs):
         lens = [int(v) for v in lens]
@@ -1614,13 +1620,63 @@ class Aligner:
         if not self.transitions:
             alpha, loglik = forward(E, lens, G)
             return backward(E, lens, G, alpha, loglik), loglik
-        alpha, loglik = forward_arcs(E, lens, G, G.w, G.edge)
-        gamma, xi = backward_arcs(E, lens, G, G.w, G.edge, alpha, loglik)
+        alpha, loglik = forward(E, lens, G, w=G.w, edge=G.edge)
+        gamma, xi = backward(E, lens, G, alpha, loglik, w=G.w, edge=G.edge)
         if tacc is not None:
             classes, kinds = G.arc_index(self.n_classes)
             tacc[0] = reduce(xi, G, self.n_classes, tacc[0], classes)
             tacc[1] = reduce(xi, G, 6, tacc[1], kinds)
         return gamma, loglik
+
+    def _e_step(self, prep, each, tacc=None, mixtures=False):
+        """The E-step of one pass over `prep` = [(features, lens, Graphs, index)].  Per batch: the features to the device, the
+        emissions (from the single-Gaussian table, or with `mixtures` from the mixture tables, with their responsibilities),
+        forward and backward under the current arc costs with the arc posteriors added to `tacc`, then `each(batch number, x, lens,
+        G, index, gamma, resp)` takes from the posteriors what the pass needs.  `batches_by_bytes` budgets for the buffers of one
+        batch: they are released before the next batch's are allocated, and `each` must keep no reference to gamma or resp.
+        -> the sum of all utterances' log-likelihoods, added batch after batch."""
+        total = 0.0
+        for i, (feats, lens, G, index) in enumerate(prep):
+            x = feats.to(self.device, non_blocking=True)
+            if mixtures:
+                resp = torch.empty(x.shape[0], x.shape[1], G.ldg, self.mixtures, dtype=torch.float64, device=self.device)
+                E = emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar, resp=resp)
+            else:
+                resp, E = None, emit(x, lens, G, self.mu, self.var)
+            gamma, loglik = self._fb(E, lens, G, tacc)
+            del E
+            each(i, x, lens, G, index, gamma, resp)
+            total += float(np.sum(loglik.cpu().numpy()))
+            del x, gamma, resp
+        return total
+
+    def _pass(self, prep, mu, var, n_frames, jac=0.0):
+        """One Baum-Welch pass of the single-Gaussian table over `prep`: the class sums, then the update of (mu, var) and of the
+        transition tables -> (the class sums, mu, var, the value the pass reports: (log-likelihood + `jac`) / n_frames, `jac` the
+        fMLLR Jacobian term)."""
+        sums, tacc = None, self._tacc()
+
+        def each(i, x, lens, G, index, gamma, resp):
+            nonlocal sums
+            sums = reduce(stats(gamma, x, lens, G), G, self.n_classes, sums, index)
+        total = self._e_step(prep, each, tacc)
+        s = sums.cpu().numpy()
+        mu, var = m_step(s, mu, var, self.floor)
+        self._set(mu, var)
+        self._trans_step(s[:, 0], tacc, prep)
+        return s, mu, var, (total + jac) / n_frames
+
+    def _initial_tables(self, s):
+        """The first table of a feature space from its first class sums s: the global mean g and variance v of their total, the
+        floor 1e-2 v, every class at (g, v), then the update -> (mu, var)."""
+        C, dim = s.shape[0], (s.shape[1] - 1) // 2
+        tot = s.sum(axis=0)
+        g_mean = tot[1:1 + dim] / tot[0]
+        g_var = tot[1 + dim:] / tot[0] - g_mean * g_mean
+        self.floor = VAR_FLOOR * g_var
+        mu, var = m_step(s, np.tile(g_mean, (C, 1)), np.tile(g_var, (C, 1)), self.floor)
+        self._set(mu, var)
+        return mu, var
 
     def _trans_step(self, n, tacc, prep):
         """The transition update after a pass with the class occupancies n, and the new arc costs on every batch of `prep`."""
@@ -1650,7 +1706,6 @@ class Aligner:
             lens, G = self._prepare(feats, lens, graphs)
             prep.append((feats, lens, G, G.index(self.n_classes, G.ldg)))
         n_frames = sum(sum(lens) for _, lens, _, _ in prep)
-        cols = 1 + 2 * self.dim
         self.loop, self.opt = np.full(self.n_classes, 0.5), np.full(3, 0.5)
         self._arcs(prep)
 
@@ -1663,34 +1718,18 @@ class Aligner:
             for b, g in enumerate(G.graphs):
                 assign[b, :lens[b]] = flat_assignment(g, lens[b])
             gamma = torch.zeros(B, Tmax, G.ldg, dtype=torch.float64, device=self.device)
-            gamma.scatter_(2, torch.from_numpy(assign).to(self.device).unsqueeze(2), 1.0)
+            gamma.scatter_(2, _up(assign, self.device).unsqueeze(2), 1.0)
             sums = reduce(stats(gamma, x, lens, G), G, self.n_classes, sums, index)
             del gamma
         if sums is None:
             raise ValueError("no utterances to train on")
         s = sums.cpu().numpy()
-        tot = s.sum(axis=0)
-        g_mean = tot[1:1 + self.dim] / tot[0]
-        g_var = tot[1 + self.dim:] / tot[0] - g_mean * g_mean
-        self.floor = VAR_FLOOR * g_var
-        mu, var = m_step(s, np.tile(g_mean, (self.n_classes, 1)), np.tile(g_var, (self.n_classes, 1)), self.floor)
-        self._set(mu, var)
+        mu, var = self._initial_tables(s)
 
         history = []
         for _ in range(iters):
-            sums, total, tacc = None, 0.0, self._tacc()
-            for feats, lens, G, index in prep:
-                x = feats.to(self.device, non_blocking=True)
-                E = emit(x, lens, G, self.mu, self.var)
-                gamma, loglik = self._fb(E, lens, G, tacc)
-                sums = reduce(stats(gamma, x, lens, G), G, self.n_classes, sums, index)
-                total += float(np.sum(loglik.cpu().numpy()))
-                del E, gamma
-            s = sums.cpu().numpy()
-            mu, var = m_step(s, mu, var, self.floor)
-            self._set(mu, var)
-            self._trans_step(s[:, 0], tacc, prep)
-            history.append(total / n_frames)
+            s, mu, var, ll = self._pass(prep, mu, var, n_frames)
+            history.append(ll)
         self._trans_log("monophones")
         if self.lda:
             prep, s, mu, var, more = self._fit_lda(prep, n_frames)
@@ -1706,10 +1745,6 @@ class Aligner:
             history += self._fit_mixtures(prep, n_frames, s[:, 0], mu, var, jac)
         return history
 
-    def _posteriors(self, x, lens, G, tacc=None):
-        """gamma and the log-likelihoods of one batch under the single-Gaussian table (and, with transitions, the arc costs)."""
-        return self._fb(emit(x, lens, G, self.mu, self.var), lens, G, tacc)
-
     def _project(self, x, lens):
         return project(splice(x, lens, self.n_mel, self.splice), lens, self.P, self.o)
 
@@ -1717,60 +1752,41 @@ class Aligner:
         """Steps 2 to 5 of the LDA schedule from the table in x -> (prep with z for the features, the class sums of the last pass,
         mu, var in z, the log-likelihood per frame of the statistics pass and of the passes in z)."""
         C, Ds, k = self.n_classes, self.splice_dim, self.lda
-        sums, sv, sm, total = None, None, None, 0.0
-        for feats, lens, G, index in prep:                                 # the statistics pass
-            x = feats.to(self.device, non_blocking=True)
-            gamma, loglik = self._posteriors(x, lens, G)
+        sums, sv, sm, zprep = None, None, None, []
+
+        def spliced(i, x, lens, G, index, gamma, resp):                    # the statistics pass
+            nonlocal sums, sv, sm
             y = splice(x, lens, self.n_mel, self.splice)
             sums = reduce(stats(gamma, y, lens, G), G, C, sums, index)
             sv, sm = scatter(y, lens, sv, sm)
-            total += float(np.sum(loglik.cpu().numpy()))
-            del gamma, y
-        history = [total / n_frames]
+        history = [self._e_step(prep, spliced) / n_frames]
         cs = sums.cpu().numpy()
         P, o, eig = lda_transform(cs[:, 0], cs[:, 1:1 + Ds], float(n_frames), sv.cpu().numpy(), sm.cpu().numpy(), k)
         print("lda: eigenvalues " + " ".join(f"{v:.4g}" for v in eig))
-        self.P = torch.from_numpy(np.ascontiguousarray(P)).to(self.device)
-        self.o = torch.from_numpy(np.ascontiguousarray(o)).to(self.device)
+        self.P, self.o = _up(P, self.device), _up(o, self.device)
 
-        sums, zprep = None, []
-        for feats, lens, G, index in prep:                                 # the same gamma on z
-            x = feats.to(self.device, non_blocking=True)
-            gamma, _ = self._posteriors(x, lens, G)
+        def projected(i, x, lens, G, index, gamma, resp):                  # the same gamma on z
+            nonlocal sums
             z = self._project(x, lens)
             sums = reduce(stats(gamma, z, lens, G), G, C, sums, index)
-            zprep.append((z.to(feats.device), lens, G, index))
-            del gamma
+            zprep.append((z.to(prep[i][0].device), lens, G, index))
+        sums = None                                                        # the statistics pass's sums on y are spent
+        self._e_step(prep, projected)
         s = sums.cpu().numpy()
-        tot = s.sum(axis=0)
-        g_mean = tot[1:1 + k] / tot[0]
-        g_var = tot[1 + k:] / tot[0] - g_mean * g_mean
-        self.floor = VAR_FLOOR * g_var
-        mu, var = m_step(s, np.tile(g_mean, (C, 1)), np.tile(g_var, (C, 1)), self.floor)
-        self._set(mu, var)
+        mu, var = self._initial_tables(s)
         for _ in range(self.lda_iters):
-            sums, total, tacc = None, 0.0, self._tacc()
-            for zf, lens, G, index in zprep:
-                z = zf.to(self.device, non_blocking=True)
-                gamma, loglik = self._posteriors(z, lens, G, tacc)
-                sums = reduce(stats(gamma, z, lens, G), G, C, sums, index)
-                total += float(np.sum(loglik.cpu().numpy()))
-                del gamma
-            s = sums.cpu().numpy()
-            mu, var = m_step(s, mu, var, self.floor)
-            self._set(mu, var)
-            self._trans_step(s[:, 0], tacc, zprep)
-            history.append(total / n_frames)
+            s, mu, var, ll = self._pass(zprep, mu, var, n_frames)
+            history.append(ll)
         self._trans_log("lda")
         return zprep, s, mu, var, history
 
     def _fit_fmllr(self, prep, speakers, n_frames, s, mu, var):
         """The fMLLR rounds from the single-Gaussian table (mu, var) on the features of `prep` -> (prep with the adapted features,
         the class sums of the last pass, mu, var, the reported value of every pass, sum_u T_u log|det A_s(u)| of the final W)."""
-        C, D = self.n_classes, mu.shape[1]
+        D = mu.shape[1]
         S = self.n_spk = 1 + max((int(sp.max()) for sp in speakers if sp.size), default=0)
         W = np.tile(np.eye(D, D + 1), (S, 1, 1))
-        self.W = torch.from_numpy(W).to(self.device)
+        self.W = _up(W, self.device)
         spk_frames = np.zeros(S)
         for (_, lens, _, _), sp in zip(prep, speakers):
             np.add.at(spk_frames, sp, np.asarray(lens, np.float64))
@@ -1778,18 +1794,17 @@ class Aligner:
         def adapted():
             return [(fmllr_apply(feats.to(self.device, non_blocking=True), lens, self.W, sp).to(feats.device), lens, G, index)
                     for (feats, lens, G, index), sp in zip(prep, speakers)]
-        hprep, history, jac = adapted(), [], 0.0
+        hprep, history, jac, acc = adapted(), [], 0.0, None
+
+        def accumulate(i, fh, lens, G, index, gamma, resp):                # the statistics pass: (beta, G, k) on the unadapted features
+            nonlocal acc
+            c, h = fmllr_weights(gamma, lens, G, self.mu, self.var)
+            acc = fmllr_accumulate(prep[i][0].to(self.device, non_blocking=True), c, h, lens, speakers[i], S, *acc)
         for rnd in range(self.fmllr_rounds):
-            beta, Gs, ks, total = None, None, None, 0.0
-            for (feats, lens, G, _), (fh, _, _, _), sp in zip(prep, hprep, speakers):      # the statistics pass
-                gamma, loglik = self._posteriors(fh.to(self.device, non_blocking=True), lens, G)
-                c, h = fmllr_weights(gamma, lens, G, self.mu, self.var)
-                beta, Gs, ks = fmllr_accumulate(feats.to(self.device, non_blocking=True), c, h, lens, sp, S, beta, Gs, ks)
-                total += float(np.sum(loglik.cpu().numpy()))
-                del gamma, c, h
-            history.append((total + jac) / n_frames)
-            W, status = fmllr_update(beta.cpu().numpy(), Gs.cpu().numpy(), ks.cpu().numpy(), W, self.fmllr_min_frames, self.fmllr_sweeps)
-            del beta, Gs, ks
+            acc = (None, None, None)
+            history.append((self._e_step(hprep, accumulate) + jac) / n_frames)
+            W, status = fmllr_update(*(t.cpu().numpy() for t in acc), W, self.fmllr_min_frames, self.fmllr_sweeps)
+            acc = None
             logdet = np.linalg.slogdet(W[:, :, :D])[1]
             jac = float(np.dot(spk_frames, logdet))
             print(f"fmllr: round {rnd + 1}, {int(np.sum(status == 0))} speakers adapted, {int(np.sum(status == 1))} kept (too few "
@@ -1797,18 +1812,8 @@ class Aligner:
             self.W.copy_(torch.from_numpy(np.ascontiguousarray(W)))
             hprep = adapted()
             for _ in range(self.fmllr_iters):
-                sums, total, tacc = None, 0.0, self._tacc()
-                for fh, lens, G, index in hprep:
-                    x = fh.to(self.device, non_blocking=True)
-                    gamma, loglik = self._posteriors(x, lens, G, tacc)
-                    sums = reduce(stats(gamma, x, lens, G), G, C, sums, index)
-                    total += float(np.sum(loglik.cpu().numpy()))
-                    del gamma
-                s = sums.cpu().numpy()
-                mu, var = m_step(s, mu, var, self.floor)
-                self._set(mu, var)
-                self._trans_step(s[:, 0], tacc, hprep)
-                history.append((total + jac) / n_frames)
+                s, mu, var, ll = self._pass(hprep, mu, var, n_frames, jac)
+                history.append(ll)
         self._trans_log("fmllr")
         return hprep, s, mu, var, history, jac
 
@@ -1830,22 +1835,16 @@ class Aligner:
         keys = np.unique(np.concatenate([k for b in ctxs for k in b]), axis=0)       # the items, sorted by (p, s, l, r)
         codes, n_items = code(keys), len(keys)
 
-        sums, total = None, 0.0                                            # the statistics pass over the items
-        for (feats, lens, G, _), kb in zip(prep, ctxs):
-            x = feats.to(self.device, non_blocking=True)
-            gamma, loglik = self._posteriors(x, lens, G)
-            Gi = Graphs([dict(g, sid=np.searchsorted(codes, code(k)).astype(np.int32)) for g, k in zip(G.graphs, kb)], self.device)
+        sums = None
+
+        def by_item(i, x, lens, G, index, gamma, resp):                    # the statistics pass over the items
+            nonlocal sums
+            Gi = Graphs([dict(g, sid=np.searchsorted(codes, code(k)).astype(np.int32)) for g, k in zip(G.graphs, ctxs[i])], self.device)
             sums = reduce(stats(gamma, x, lens, G), Gi, n_items, sums, Gi.index(n_items, G.ldg))
-            total += float(np.sum(loglik.cpu().numpy()))
-            del gamma
-        history = [(total + jac) / n_frames]
+        history = [(self._e_step(prep, by_item) + jac) / n_frames]
 
         def pooled(classes, n):                                            # class sums of the item table, items ascending
-            order = np.argsort(classes, kind="stable")
-            offs = np.zeros(n + 1, np.int64)
-            np.cumsum(np.bincount(classes, minlength=n), out=offs[1:])
-            index = (torch.from_numpy(offs.astype(np.int32)).to(self.device), torch.from_numpy(order.astype(np.int32)).to(self.device))
-            return reduce(sums.view(1, n_items, cols), None, n, None, index).cpu().numpy()
+            return reduce(sums.view(1, n_items, cols), None, n, None, _csr(classes, n, self.device)).cpu().numpy()
         roots = keys[:, 0].astype(np.int64) * S + keys[:, 1]
         ci = sorted(self.phone_ids[p] for p in (SIL, SP, SPN))
         if self.question_sets is not None:
@@ -1854,15 +1853,12 @@ class Aligner:
             names, member = phone_questions(pooled(roots, C0), [p for p in range(C0 // S) if p not in ci], S, self.floor, n_sym)
         if not 1 <= len(names) <= max_tree_sets():
             raise ValueError(f"{len(names)} question sets, supported are 1..{max_tree_sets()}")
-        left = torch.from_numpy(keys[:, 2].astype(np.int32)).to(self.device)
-        right = torch.from_numpy(keys[:, 3].astype(np.int32)).to(self.device)
-        member_d, floor_d = torch.from_numpy(member).to(self.device), torch.from_numpy(np.ascontiguousarray(self.floor)).to(self.device)
+        left, right = _up(keys[:, 2].astype(np.int32), self.device), _up(keys[:, 3].astype(np.int32), self.device)
+        member_d, floor_d = _up(member, self.device), _up(self.floor, self.device)
 
         def gains_of(nodes):                                               # one launch per level
-            offs = np.zeros(len(nodes) + 1, np.int64)
-            np.cumsum([len(it) for it in nodes], out=offs[1:])
-            q, g = tree_gains(sums, left, right, torch.from_numpy(offs.astype(np.int32)).to(self.device),
-                              torch.from_numpy(np.concatenate(nodes).astype(np.int32)).to(self.device), member_d, floor_d, self.tri_min_occ)
+            offs, items = _csr(np.repeat(np.arange(len(nodes)), [len(it) for it in nodes]), len(nodes), self.device, np.concatenate(nodes))
+            q, g = tree_gains(sums, left, right, offs, items, member_d, floor_d, self.tri_min_occ)
             return q.cpu().numpy(), g.cpu().numpy()
         full = tree_build(keys, roots, C0, [p * S + st for p in ci for st in range(S)], member, gains_of, self.tri_min_gain)
         question, yes, no, leaf, gain = tree_replay(full, C0, self.triphones)
@@ -1881,28 +1877,15 @@ class Aligner:
         self._set(mu, var)
         self.loop = self.loop[leaf_root]                                   # a leaf starts from its root's self-loop probability
         if self.mixtures > 1:
-            self.gw = torch.zeros(n_leaves, self.mixtures, dtype=torch.float64, device=self.device)
-            self.gw[:, 0] = 1.0
-            self.gmu = torch.zeros(n_leaves, self.mixtures, D, dtype=torch.float64, device=self.device)
-            self.gvar = torch.ones(n_leaves, self.mixtures, D, dtype=torch.float64, device=self.device)
+            self._mixture_tables(n_leaves, D)
         lprep = []
         for (feats, lens, G, _), kb in zip(prep, ctxs):
             Gl = Graphs([dict(g, sid=item_leaf[np.searchsorted(codes, code(k))].astype(np.int32)) for g, k in zip(G.graphs, kb)], self.device)
             lprep.append((feats, lens, Gl, Gl.index(n_leaves, Gl.ldg)))
         self._arcs(lprep)
         for _ in range(self.tri_iters):
-            sums, total, tacc = None, 0.0, self._tacc()
-            for feats, lens, G, index in lprep:
-                x = feats.to(self.device, non_blocking=True)
-                gamma, loglik = self._posteriors(x, lens, G, tacc)
-                sums = reduce(stats(gamma, x, lens, G), G, n_leaves, sums, index)
-                total += float(np.sum(loglik.cpu().numpy()))
-                del gamma
-            s = sums.cpu().numpy()
-            mu, var = m_step(s, mu, var, self.floor)
-            self._set(mu, var)
-            self._trans_step(s[:, 0], tacc, lprep)
-            history.append((total + jac) / n_frames)
+            s, mu, var, ll = self._pass(lprep, mu, var, n_frames, jac)
+            history.append(ll)
         self._trans_log("triphones")
         return lprep, s, mu, var, history
 
@@ -1914,24 +1897,24 @@ class Aligner:
         w[:, 0], gmu[:, 0], gvar[:, 0] = 1.0, mu, var
         ncomp, occ = np.ones(C, np.int64), np.zeros((C, M))
         occ[:, 0] = occ0
-        index = [G.index(C, G.ldg, M) for _, _, G, _ in prep]
-        history = []
+        mprep = [(feats, lens, G, G.index(C, G.ldg, M)) for feats, lens, G, _ in prep]
+        history, sums = [], None
+
+        def each(i, x, lens, G, index, gamma, resp):
+            nonlocal sums
+            sums = reduce(stats_gmm(gamma, resp, x, lens, G), G, C, sums, index)
+
+        def set_tables():
+            for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
+                dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
         for k in range(1, M):
             w, gmu, gvar, ncomp = split_classes(w, gmu, gvar, ncomp, occ, k, self.min_split_occ)
             print(f"mixtures: stage {k + 1}, classes by active components " +
                   " ".join(f"{n}:{int(np.sum(ncomp == n))}" for n in range(1, M + 1) if np.any(ncomp == n)))
             for _ in range(self.mix_iters):
-                for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
-                    dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
-                sums, total, tacc = None, 0.0, self._tacc()
-                for (feats, lens, G, _), idx in zip(prep, index):
-                    x = feats.to(self.device, non_blocking=True)
-                    resp = torch.empty(x.shape[0], x.shape[1], G.ldg, M, dtype=torch.float64, device=self.device)
-                    E = emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar, resp=resp)
-                    gamma, loglik = self._fb(E, lens, G, tacc)
-                    sums = reduce(stats_gmm(gamma, resp, x, lens, G), G, C, sums, idx)
-                    total += float(np.sum(loglik.cpu().numpy()))
-                    del E, gamma, resp
+                set_tables()
+                sums, tacc = None, self._tacc()
+                total = self._e_step(mprep, each, tacc, mixtures=True)
                 s = sums.cpu().numpy().reshape(C, M, 1 + 2 * D)
                 occ = s[:, :, 0]
                 w, gmu, gvar = m_step_gmm(s, w, gmu, gvar, ncomp, self.floor)
@@ -1942,8 +1925,7 @@ class Aligner:
                     self._trans_step(n_c, tacc, prep)
                 history.append((total + jac) / n_frames)
             self._trans_log(f"mixtures stage {k + 1}")
-        for dst, src in ((self.gw, w), (self.gmu, gmu), (self.gvar, gvar)):
-            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+        set_tables()
         self.ncomp = ncomp
         return history
 
@@ -1968,9 +1950,7 @@ class Aligner:
         E = emit(x, lens, G, self.mu, self.var) if self.mixtures == 1 else emit_gmm(x, lens, G, self.gw, self.gmu, self.gvar)
         if self.transitions:
             G.set_arcs(self.loop, self.opt)
-            bp, end, vit = viterbi_arcs(E, lens, G, G.w, G.edge)
-        else:
-            bp, end, vit = viterbi(E, lens, G)
+        bp, end, vit = viterbi(E, lens, G, w=G.w, edge=G.edge)             # no costs (None) without transitions
         return x, lens, G, bp, end, vit
 
     def align(self, feats, lens, graphs, speakers=None):
@@ -2045,8 +2025,8 @@ class Aligner:
                 seg[b, :len(g["blocks"])] = segment_table(g, state[b, :n])
                 cand[b, :len(g["blocks"])] = self.candidates(g)
             arc = np.stack([np.log(self.loop), np.log(1.0 - self.loop)], 1) if self.transitions else np.zeros((self.n_classes, 2))
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)       # noqa: E731
-            V = segment_scores(x, lens, up(seg), up(cand).reshape(len(graphs), -1, P, S), *tables, up(arc)).cpu().numpy()
+            dev = self.device
+            V = segment_scores(x, lens, _up(seg, dev), _up(cand, dev).reshape(len(graphs), -1, P, S), *tables, _up(arc, dev)).cpu().numpy()
             for b, g in enumerate(graphs):
                 nb = len(g["blocks"])
                 out[b]["V"] = V[b, :nb].copy()
@@ -2081,11 +2061,6 @@ def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmll
     return ragged.greedy_batches(list(zip(frames, states)), budget, cost)
 
 
-def fmllr_dim_message(dim, lda):
-    return (f"fmllr adapts at most {max_fmllr_dim()} feature dimensions (a speaker's statistics are D (D + 1)(D + 2) doubles), got {dim}"
-            + ("" if lda else f": with {dim // 2} mel channels --fmllr needs --lda k with k <= {max_fmllr_dim()}"))
-
-
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
           batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
           fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0,
@@ -2101,35 +2076,26 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     from . import audio as Audio
     from .preprocess import load_wav
     dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
-    if not 1 <= mixtures <= max_mixtures():
-        raise ValueError(f"mixtures must be 1..{max_mixtures()}, got {mixtures}")
-    if transitions not in (0, 1):
-        raise ValueError(f"transitions must be 0 or 1, got {transitions}")
     if seg_scores not in (0, 1) or (seg_scores and scores is None):
         raise ValueError(f"seg_scores must be 0 or 1 and needs `scores`, got {seg_scores} with scores = {scores}")
     raw, out_dir = config["path"]["raw_path"], os.path.join(config["path"]["preprocessed_path"], "TextGrid")
     pp = config["preprocessing"]
     sr, hop, n_mel = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"], pp["mel"]["n_mel_channels"]
-    Ds = splice_dim(n_mel, splice, lda) if lda else 0                      # refuses a bad --lda / --splice before any work
-    Df = (lda if lda else 2 * n_mel) if fmllr else 0
+    _, Ds, Dt = check_options(2 * n_mel, mixtures, mix_iters, lda, splice, lda_iters, fmllr, fmllr_rounds, fmllr_iters, fmllr_sweeps,
+                              fmllr_min_frames, triphones, tri_iters, tri_min_occ, tri_min_gain, transitions)  # before any file is read
+    Df = Dt if fmllr else 0
     speakers = sorted(d for d in os.listdir(raw) if os.path.isdir(os.path.join(raw, d)))
-    if fmllr:
-        if not 1 <= Df <= max_fmllr_dim():
-            raise ValueError(fmllr_dim_message(Df, lda))
-        if len(speakers) * Df * (Df + 1) * (Df + 2) * 8 > resident_bytes:
-            raise ValueError(f"the fmllr statistics of {len(speakers)} speakers in {Df} dimensions take "
-                             f"{len(speakers) * Df * (Df + 1) * (Df + 2) * 8} bytes, more than resident_bytes = {resident_bytes}")
+    if fmllr and len(speakers) * Df * (Df + 1) * (Df + 2) * 8 > resident_bytes:
+        raise ValueError(f"the fmllr statistics of {len(speakers)} speakers in {Df} dimensions take "
+                         f"{len(speakers) * Df * (Df + 1) * (Df + 2) * 8} bytes, more than resident_bytes = {resident_bytes}")
     speaker_ids = {name: i for i, name in enumerate(speakers)}
     lexicon = read_lexicon(config["path"]["lexicon_path"])
     phone_ids = phone_table(lexicon)
     if seg_scores and len(phone_ids) > max_seg_phones():
         raise ValueError(f"seg_scores takes at most {max_seg_phones()} phones, the lexicon has {len(phone_ids)}")
     if triphones:
-        if not float(tri_min_occ) >= 1.0:
-            raise ValueError(f"tri_min_occ must be at least 1, got {tri_min_occ}")
-        if triphones < len(phone_ids) * states:
-            raise ValueError(f"triphones = {triphones} leaves is below the {len(phone_ids) * states} roots and fixed leaves")
-        real, Dt = len(phone_ids) - 3, lda if lda else 2 * n_mel           # the item table: at most R S (R + 1)^2 + 3 S rows of 1 + 2 D
+        check_leaves(triphones, len(phone_ids) * states)
+        real = len(phone_ids) - 3                                          # the item table: at most R S (R + 1)^2 + 3 S rows of 1 + 2 D
         table = (real * states * (real + 1) ** 2 + 3 * states) * (1 + 2 * Dt) * 8
         if table > resident_bytes:
             raise ValueError(f"the item table of {real} phones with {states} states in {Dt} dimensions may take {table} bytes, more "
