@@ -23,9 +23,16 @@ normalised, as the reference does to LJSpeech.  The filter, the cast (a positive
 reference) and the one deviation (an all-zero file yields zeros, with a warning, where the reference divides by zero) are specified
 in fastspeech2_amd/resample.py.
 
+Loudness.  `normalize="loudness"` replaces the last two steps of the device stage by `peak_abs` -> `loudness.block_energy` ->
+`integrated` -> `gain` -> `gain_pcm`: every utterance goes to `target_lufs` (ITU-R BS.1770-4 integrated loudness), the gain bounded by
+the `ceiling_db` sample-peak ceiling, with a rounding, saturating cast (fastspeech2_amd/loudness.py).  The default stays `"peak"`, with
+which nothing above changes.
+
 `audio_fn(wavs, sr_in, sr_out, max_wav_value) -> [int16 arrays]` replaces the device stage (the seam `Preprocessor` has in
 `pitch_fn`), so walkers, text and file layout can be exercised without a GPU.
 """
+import json
+import math
 import os
 import warnings
 from concurrent.futures import ThreadPoolExecutor
@@ -85,30 +92,102 @@ def _walker(config):
 
 # ------------------------------------------------------------------------------------------------ device stage
 class _DeviceAudio:
-    """audio_fn on the GPU: [float32 1-D] at sr_in -> [int16 1-D] at sr_out, peak-normalised; one H2D and one D2H copy per call."""
+    """audio_fn on the GPU: [float32 1-D] at sr_in -> [int16 1-D] at sr_out, peak-normalised or (normalize="loudness") brought to
+    `target_lufs` under the `ceiling_db` sample-peak ceiling; one H2D and one D2H copy of audio per call.  After a loudness call
+    `measurements` holds one dict per utterance of that call (the keys of `--report`, without `wav`)."""
 
-    def __init__(self, device):
+    def __init__(self, device, normalize="peak", target_lufs=-23.0, ceiling_db=-1.0):
         self.device = ragged.require_device(torch.device(device), "fastspeech2_amd.prepare_align (without an audio_fn)")
         self._staging = ragged.Staging()
+        self.normalize, self.target_lufs, self.ceiling_db = normalize, target_lufs, ceiling_db
+        self.measurements = None
 
     def __call__(self, wavs, sr_in, sr_out, max_wav_value):
         from . import resample as R
         self._staging.pack(wavs)
         y, out_lens = R.resample_poly(self._staging.to(self.device), [len(w) for w in wavs], sr_in, sr_out)
+        if self.normalize == "loudness":
+            return self._loudness(y, out_lens, sr_out)
         pcm = R.peaknorm_pcm(y, out_lens, R.peak_abs(y, out_lens), max_wav_value).cpu().numpy()   # orders after the kernels
         return [pcm[b, :n].copy() for b, n in enumerate(out_lens.tolist())]
 
+    def _loudness(self, y, out_lens, sr):
+        """peak_abs -> block_energy -> integrated -> gain -> gain_pcm; the int16 rows and the per-utterance numbers (fp64: loudness,
+        gain, flags, saturated count) leave the device in one buffer."""
+        from . import loudness as L, resample as R
+        B, N = y.shape
+        peak = R.peak_abs(y, out_lens)
+        loud = L.integrated(*L.block_energy(y, out_lens, sr))
+        g, flags = L.gain(loud, peak, self.target_lufs, self.ceiling_db)
+        buf = torch.empty(B * 4 * 8 + B * N * 2, dtype=torch.uint8, device=y.device)
+        stats, pcm = buf[:B * 32].view(torch.float64).view(B, 4), buf[B * 32:].view(torch.int16).view(B, N)
+        _, sat = L.gain_pcm(y, out_lens, g, out=pcm)
+        stats.copy_(torch.stack([loud[:, 0], g, flags.double(), sat.double()], dim=1))
+        host = buf.cpu()                                                     # orders after the kernels
+        stats, pcm = host[:B * 32].view(torch.float64).view(B, 4).tolist(), host[B * 32:].view(torch.int16).view(B, N).numpy()
+        out = [pcm[b, :n].copy() for b, n in enumerate(out_lens.tolist())]
+        self.measurements = []
+        for (lufs, gain, flag, clipped), row in zip(stats, out):
+            gain_db = 20.0 * math.log10(gain) if gain > 0 else None
+            fallback = bool(int(flag) & 2)
+            peak_out = int(np.abs(row.astype(np.int32)).max()) if len(row) else 0
+            self.measurements.append({
+                "lufs_in": lufs if math.isfinite(lufs) else None,
+                "lufs_out": lufs + gain_db if not fallback and gain_db is not None else None,
+                "gain_db": gain_db, "limited": bool(int(flag) & 1), "fallback": fallback, "clipped": int(clipped),
+                "sample_peak_dbfs_out": 20.0 * math.log10(peak_out / 32768.0) if peak_out else None})
+        return out
+
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
-def prepare_align(config, device="cuda", audio_fn=None, batch_seconds=1500.0, num_workers=8):
-    """Write `raw_path` from `corpus_path`; returns the number of utterances written."""
+NORMALIZE = ("peak", "loudness")
+REPORT_KEYS = ("wav", "lufs_in", "lufs_out", "gain_db", "limited", "fallback", "clipped", "sample_peak_dbfs_out")
+
+
+def _summary(rows, out_dir):
+    """lines for stdout: mean and spread of the input loudness per speaker directory, then the limited and fallback counts"""
+    by_spk = {}
+    for r in rows:
+        by_spk.setdefault(os.path.relpath(os.path.dirname(r["wav"]), out_dir), []).append(r["lufs_in"])
+    lines = []
+    for spk in sorted(by_spk):
+        v = np.array([x for x in by_spk[spk] if x is not None], dtype=np.float64)
+        if len(v):
+            lines.append(f"{spk}: {len(by_spk[spk])} files, input loudness mean {v.mean():.2f} LUFS, std {v.std():.2f}, "
+                         f"range {v.min():.2f} .. {v.max():.2f}")
+        else:
+            lines.append(f"{spk}: {len(by_spk[spk])} files, none long and loud enough to measure")
+    lines.append(f"{sum(r['limited'] for r in rows)} of {len(rows)} files limited by the peak ceiling, "
+                 f"{sum(r['fallback'] for r in rows)} without a loudness (shorter than 400 ms or silent: set to the ceiling)")
+    return lines
+
+
+def prepare_align(config, device="cuda", audio_fn=None, batch_seconds=1500.0, num_workers=8, normalize="peak", target_lufs=-23.0,
+                  ceiling_db=-1.0, report=None):
+    """Write `raw_path` from `corpus_path`; returns the number of utterances written.
+
+    normalize="peak" (the default) is the reference's `wav / max|wav| * max_wav_value`.  normalize="loudness" brings every utterance
+    to `target_lufs` (integrated loudness, ITU-R BS.1770-4: fastspeech2_amd/loudness.py) unless that would take its sample peak above
+    `ceiling_db` dBFS, in which case the ceiling sets the gain; an utterance without a loudness (shorter than 400 ms, or silent) is
+    set to the ceiling.  `report`: a file that receives one JSON object per written wav (REPORT_KEYS), one per line; a summary goes
+    to stdout.  Loudness normalisation belongs to the device stage and cannot be combined with an `audio_fn`."""
+    if normalize not in NORMALIZE:
+        raise ValueError(f"normalize must be one of {NORMALIZE}, got {normalize!r}")
+    if normalize == "loudness":
+        from .loudness import check_options
+        check_options(target_lufs, ceiling_db)
+        if audio_fn is not None:
+            raise ValueError('normalize="loudness" runs in the device stage: it cannot be combined with an audio_fn')
+    elif report is not None:
+        raise ValueError('report is written by normalize="loudness" only')
     in_dir, out_dir = config["path"]["corpus_path"], config["path"]["raw_path"]
     sampling_rate = config["preprocessing"]["audio"]["sampling_rate"]
     max_wav_value = config["preprocessing"]["audio"]["max_wav_value"]
     cleaners = config["preprocessing"]["text"]["text_cleaners"]
     walk = _walker(config)
     if audio_fn is None:
-        audio_fn = _DeviceAudio(device)
+        audio_fn = _DeviceAudio(device, normalize, target_lufs, ceiling_db)
+    rows = []
     batch_samples = int(batch_seconds * sampling_rate)
     written = 0
     window, window_samples = [], 0                                          # (out_wav, source rate, float32 waveform)
@@ -119,6 +198,8 @@ def prepare_align(config, device="cuda", audio_fn=None, batch_seconds=1500.0, nu
         for sr, ks in ragged.keyed_batches([w[1] for w in window], [(len(w[2]),) for w in window],
                                            lambda sr: batch_samples * sr // sampling_rate, ragged.padded_samples):
             pcms = audio_fn([window[k][2] for k in ks], sr, sampling_rate, max_wav_value)
+            if normalize == "loudness":
+                rows.extend(dict(wav=window[k][0], **m) for k, m in zip(ks, audio_fn.measurements))
             for k, pcm in zip(ks, pcms):
                 from scipy.io import wavfile
                 pcm = np.asarray(pcm)
@@ -158,4 +239,10 @@ def prepare_align(config, device="cuda", audio_fn=None, batch_seconds=1500.0, nu
                 drain()
         drain()
         flush()
+    if normalize == "loudness":
+        if report is not None:
+            with open(report, "w") as f:
+                for r in rows:
+                    f.write(json.dumps(r) + "\n")
+        print("\n".join(_summary(rows, out_dir)))
     return written
