@@ -42,6 +42,12 @@ if __name__ == "__main__":
                              "Young's definition), the best rival phone and the margin to every phone entry")
     parser.add_argument("--g2p_model", type=str, default=None,
                         help="a model trained by `python g2p.py train`: an out-of-lexicon word gets its pronunciation instead of spn")
+    parser.add_argument("--save_model", type=str, default=None,
+                        help="write the trained model to this .npz file (tables, options, phone table, feature settings, speaker names, "
+                             "phone bigram counts) for --model and for recognize.py")
+    parser.add_argument("--model", type=str, default=None,
+                        help="align with this model file instead of training one (`mfa align`); training options beside it are an error, "
+                             "and so are a lexicon or feature settings that are not the model's")
     parser.add_argument("--overwrite", action="store_true", help="replace TextGrids that exist already")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_gib", type=float, default=8.0, help="device buffers per ragged batch")
@@ -59,8 +65,12 @@ if __name__ == "__main__":
                                           fmllr_sweeps=args.fmllr_sweeps, fmllr_min_frames=args.fmllr_min_frames,
                                           triphones=args.triphones, tri_iters=args.tri_iters, tri_min_occ=args.tri_min_occ,
                                           tri_min_gain=args.tri_min_gain, questions=args.questions, transitions=args.transitions, scores=args.scores,
-                                          g2p=args.g2p_model, seg_scores=args.seg_scores)
+                                          g2p=args.g2p_model, seg_scores=args.seg_scores, save_model=args.save_model, model=args.model)
     except FileExistsError as e:
+        sys.exit(str(e))
+    except ValueError as e:
+        if args.model is None:
+            raise
         sys.exit(str(e))
     print("log-likelihood per frame: " + " ".join("{:.4f}".format(h) for h in history))
     print("{} TextGrids written, {} utterances skipped".format(written, len(skipped)))

@@ -306,6 +306,17 @@ over the number of frames, every q scored as a whole HMM over the same segment, 
   What is claimed.  The published definition, pinned to a numpy restatement (tests/align_seg_ref.py).  No threshold.  Nothing has
   been measured on real speech, against MFA or against Kaldi's `compute-gop`, and no timing measured yet.
 
+Model files (`save_model` / `model`; without them every launch, number and byte is everything above, unchanged).  `Aligner.save`
+writes one .npz without pickled objects: the tables the decoding model uses (mu / var, or gw / gmu / gvar / ncomp; P / o; W; the
+tree's arrays; loop / opt; floor), the constructor options, the phone table in id order, the feature settings the model was trained
+under (sampling rate, filter / hop / win length, n_mel, fmin, fmax), with `fmllr` the speaker names in index order, the phone bigram
+counts of the training corpus's decoded alignments (a sequence is the blocks with frames > 0, the realised `sil` / `sp` included;
+fastspeech2_amd/recognize.py) and MODEL_VERSION.  `Aligner.load` rebuilds an `Aligner` whose `align` and `score` return the bits of
+the original's.  `build(..., model=file)` trains nothing (the history is []) and aligns the corpus with the loaded model; it
+refuses, with a ValueError naming the difference and before any audio is read, training options beside the file, a lexicon whose
+phone table is not the model's, feature settings that are not the model's and, with `fmllr`, a speaker directory the model has no
+transform for (estimating transforms for new speakers is not built).
+
 Determinism.  No floating-point atomics.  Per utterance the sums go to partials [J][1 + 2 D], each summed in ascending t; the class
 sums add those rows in the order of a host-built (class -> [(utterance, state)]) list, batch after batch in a fixed order; the
 update runs on the host in numpy.  Every sum's order is a function of the batch shape (for the speaker statistics: and of the
@@ -2033,6 +2044,109 @@ class Aligner:
                 out[b]["seg"], out[b]["gop_seg"] = segment_reductions(g, seg[b, :nb], out[b]["V"])
         return [frames[b, :len(g["blocks"])].copy() for b, g in enumerate(graphs)], out
 
+    def options(self):
+        """The constructor's keyword arguments (without the device, the questions file and the phone table)."""
+        return {"n_classes": self.n_mono, "dim": self.dim, "states": self.states, "mixtures": self.mixtures, "mix_iters": self.mix_iters,
+                "min_split_occ": self.min_split_occ, "lda": self.lda, "splice": self.splice, "lda_iters": self.lda_iters,
+                "fmllr": self.fmllr, "fmllr_rounds": self.fmllr_rounds, "fmllr_iters": self.fmllr_iters, "fmllr_sweeps": self.fmllr_sweeps,
+                "fmllr_min_frames": self.fmllr_min_frames, "triphones": self.triphones, "tri_iters": self.tri_iters,
+                "tri_min_occ": self.tri_min_occ, "tri_min_gain": self.tri_min_gain, "transitions": self.transitions}
+
+    def save(self, path, phone_names, feature_config, speaker_names=None, bigram=None):
+        """The trained model as one .npz (no pickled objects): every table `align` and `score` use (mu, var, or with mixtures gw, gmu,
+        gvar, ncomp; the LDA's P, o; the speaker transforms W; the tree's arrays; loop, opt; floor), the constructor options, the phone
+        table in id order, the feature configuration the model was trained under (`recognize.feature_config`), with fmllr the
+        speaker names in index order, the bigram counts of `recognize.phone_bigram` (or none) and MODEL_VERSION."""
+        phone_names = [str(p) for p in phone_names]
+        if len(phone_names) * self.states != self.n_mono:
+            raise ValueError(f"{len(phone_names)} phone names for a model of {self.n_mono // self.states} phones")
+        if self.lda and self.P is None or self.fmllr and self.W is None or self.triphones and self.tree is None:
+            raise ValueError("the model has not been trained: `fit` comes before `save`")
+        host = lambda t: t.cpu().numpy()                                                   # noqa: E731
+        out = {"version": np.array(MODEL_VERSION), "options": np.array(json.dumps(self.options())),
+               "features": np.array(json.dumps(dict(feature_config))), "phones": np.array(phone_names),
+               "floor": np.asarray(self.floor, np.float64), "loop": np.asarray(self.loop, np.float64), "opt": np.asarray(self.opt, np.float64)}
+        if self.mixtures == 1:
+            out.update(mu=host(self.mu), var=host(self.var))
+        else:
+            out.update(gw=host(self.gw), gmu=host(self.gmu), gvar=host(self.gvar), ncomp=np.asarray(self.ncomp, np.int64))
+        if self.lda:
+            out.update(P=host(self.P), o=host(self.o))
+        if self.fmllr:
+            names = [str(s) for s in (speaker_names if speaker_names is not None else [])]
+            if len(names) != self.n_spk:
+                raise ValueError(f"a model with fmllr has {self.n_spk} speaker transforms, {len(names)} speaker names were given")
+            out.update(W=host(self.W), speakers=np.array(names))
+        if self.triphones:
+            t = self.tree
+            out.update({"tree_" + k: np.asarray(t[k]) for k in ("question", "yes", "no", "leaf", "member")})
+            out.update(tree_names=np.array([str(n) for n in t["names"]]), tree_numbers=np.array([t["gain"], t["n_items"], t["n_leaves"]], np.float64))
+        if bigram is not None:
+            out["bigram"] = np.asarray(bigram, np.float64)
+        with open(path, "wb") as f:                                        # np.savez would append .npz to a bare name
+            np.savez(f, **out)
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """The `Aligner` a file of `save` holds: its `align` and `score` return the bits of the original's.  The file's metadata are
+        attributes: phone_names, feature_config, speaker_names (None without fmllr), bigram (None when the file has none)."""
+        with np.load(path, allow_pickle=False) as f:
+            d = {k: f[k] for k in f.files}
+        if "version" not in d or int(d["version"]) != MODEL_VERSION:
+            raise ValueError(f"{path} is not a model file of format {MODEL_VERSION}")
+        opts, names = json.loads(str(d["options"])), [str(p) for p in d["phones"]]
+        al = cls(device=device, phone_ids={p: i for i, p in enumerate(names)} if opts["triphones"] else None, **opts)
+        al.phone_names, al.feature_config = names, json.loads(str(d["features"]))
+        al.speaker_names = [str(s) for s in d["speakers"]] if al.fmllr else None
+        al.bigram = d.get("bigram")
+        al.floor, al.loop, al.opt = d["floor"], d["loop"], d["opt"]
+        al.n_classes = len(al.loop)
+        if al.mixtures == 1:
+            al._set(d["mu"], d["var"])
+        else:
+            al.gw, al.gmu, al.gvar, al.ncomp = _up(d["gw"], al.device), _up(d["gmu"], al.device), _up(d["gvar"], al.device), d["ncomp"]
+        if al.lda:
+            al.P, al.o = _up(d["P"], al.device), _up(d["o"], al.device)
+        if al.fmllr:
+            al.W, al.n_spk = _up(d["W"], al.device), d["W"].shape[0]
+        if al.triphones:
+            gain, n_items, n_leaves = d["tree_numbers"]
+            al.tree = {**{k: d["tree_" + k] for k in ("question", "yes", "no", "leaf", "member")}, "names": [str(n) for n in d["tree_names"]],
+                       "gain": float(gain), "n_items": int(n_items), "n_leaves": int(n_leaves)}
+        return al
+
+
+MODEL_VERSION = 1
+TRAINING_DEFAULTS = dict(states=2, iters=12, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2, fmllr_iters=2,
+                         fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0, questions=None,
+                         transitions=0)
+
+
+def _load_for(model, dev, config, phone_ids, speakers, given):
+    """The model file `build(model=...)` decodes with, after its refusals: training options beside it, a phone table, feature
+    settings or a speaker it was not trained with -> (Aligner, speaker name -> its index in the model)."""
+    from .recognize import feature_config
+    extra = sorted(k for k, v in given.items() if v != TRAINING_DEFAULTS[k])
+    if extra:
+        raise ValueError(f"training options ({', '.join(extra)}) cannot be given together with a model file: it is not trained again")
+    al = Aligner.load(model, dev)
+    table = sorted(phone_ids, key=phone_ids.get)
+    if table != al.phone_names:
+        here, there = set(table) - set(al.phone_names), set(al.phone_names) - set(table)
+        raise ValueError(f"the lexicon's phone table is not the model's: only in the lexicon {sorted(here)}, only in the model {sorted(there)}"
+                         if here or there else "the lexicon's phone table is the model's in another order")
+    fc = feature_config(config)
+    if fc != al.feature_config:
+        diff = ", ".join(f"{k} {fc[k]} (model: {al.feature_config.get(k)})" for k in fc if fc[k] != al.feature_config.get(k))
+        raise ValueError(f"the config's feature settings are not the model's: {diff}")
+    ids = {name: i for i, name in enumerate(speakers)}
+    if al.fmllr:
+        unknown = [s for s in speakers if s not in al.speaker_names]
+        if unknown:
+            raise ValueError(f"the model has no fmllr transform for the speakers {unknown} (it was trained with {al.speaker_names})")
+        ids = {name: al.speaker_names.index(name) for name in speakers}
+    return al, ids
+
 
 # ------------------------------------------------------------------------------------------------ the corpus pass
 def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmllr_dim=0, transitions=0, seg_phones=0, block_states=2):
@@ -2064,7 +2178,7 @@ def batches_by_bytes(frames, states, dim, budget, mixtures=1, splice_dim=0, fmll
 def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_bytes=8 << 30, resident_bytes=16 << 30,
           batch_seconds=1800.0, num_workers=8, mixtures=1, mix_iters=4, lda=0, splice=3, lda_iters=4, fmllr=0, fmllr_rounds=2,
           fmllr_iters=2, fmllr_sweeps=20, fmllr_min_frames=500, triphones=0, tri_iters=4, tri_min_occ=100, tri_min_gain=0.0,
-          questions=None, transitions=0, scores=None, g2p=None, seg_scores=0):
+          questions=None, transitions=0, scores=None, g2p=None, seg_scores=0, save_model=None, model=None):
     """Align every `{raw_path}/{speaker}/{basename}.wav` that has a `.lab` and write its TextGrid.  Returns (written, skipped,
     log-likelihood per frame of every pass); `skipped` lists (speaker, basename, reason).  `scores` = a path: decoding goes through
     `Aligner.score` and one JSON object per written utterance goes to that file (the "Confidence" paragraph): speaker, basename,
@@ -2072,7 +2186,12 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     `g2p` = a `fastspeech2_amd.g2p.G2P` model or the path of one: out-of-lexicon words get its pronunciation instead of `spn`
     (`pronounce_oov`, one batched decode of the corpus's OOV words before any graph is built); the count is printed.
     `seg_scores` = 1 (needs `scores`): the "Segmental scores" paragraph; every phone entry becomes [label, start_s, end_s, loglik, gop,
-    match, gop_seg, rival_label, margin] and the utterance object gains gop_seg.  With 0 the scores file is what it was."""
+    match, gop_seg, rival_label, margin] and the utterance object gains gop_seg.  With 0 the scores file is what it was.
+    `save_model` = a path: after `fit` the model goes to that file (`Aligner.save`) with the phone table, the feature settings, the
+    speaker names and the bigram counts of the decoded alignments (fastspeech2_amd/recognize.py).  `model` = such a file: nothing
+    is trained (the history is []), the corpus is aligned with the loaded model; training options beside it, a lexicon whose
+    phone table is not the model's, other feature settings or, with fmllr, a speaker the model has no transform for are
+    ValueErrors before any audio is read."""
     from . import audio as Audio
     from .preprocess import load_wav
     dev = ragged.require_device(torch.device(device), "fastspeech2_amd.align")
@@ -2091,6 +2210,17 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     speaker_ids = {name: i for i, name in enumerate(speakers)}
     lexicon = read_lexicon(config["path"]["lexicon_path"])
     phone_ids = phone_table(lexicon)
+    aligner = None
+    if model is not None:
+        if save_model is not None:
+            raise ValueError("save_model and model are not given together: a loaded model is not trained")
+        given = dict(states=states, iters=iters, mixtures=mixtures, mix_iters=mix_iters, lda=lda, splice=splice, lda_iters=lda_iters,
+                     fmllr=fmllr, fmllr_rounds=fmllr_rounds, fmllr_iters=fmllr_iters, fmllr_sweeps=fmllr_sweeps,
+                     fmllr_min_frames=fmllr_min_frames, triphones=triphones, tri_iters=tri_iters, tri_min_occ=tri_min_occ,
+                     tri_min_gain=tri_min_gain, questions=questions, transitions=transitions)
+        aligner, speaker_ids = _load_for(model, dev, config, phone_ids, speakers, given)
+        states, mixtures, transitions, fmllr = aligner.states, aligner.mixtures, aligner.transitions, aligner.fmllr
+        Ds, Df = aligner.splice_dim, (aligner.lda or 2 * n_mel) if fmllr else 0
     if seg_scores and len(phone_ids) > max_seg_phones():
         raise ValueError(f"seg_scores takes at most {max_seg_phones()} phones, the lexicon has {len(phone_ids)}")
     if triphones:
@@ -2181,16 +2311,19 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
             feats[r, :frames[i]] = items[i]["x"]
             items[i]["x"] = None
         packed.append((feats.to(dev) if resident else feats, [frames[i] for i in batch], [items[i]["graph"] for i in batch], batch))
-    aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters, lda=lda, splice=splice, lda_iters=lda_iters,
-                      fmllr=fmllr, fmllr_rounds=fmllr_rounds, fmllr_iters=fmllr_iters, fmllr_sweeps=fmllr_sweeps,
-                      fmllr_min_frames=fmllr_min_frames, triphones=triphones, tri_iters=tri_iters, tri_min_occ=tri_min_occ,
-                      tri_min_gain=tri_min_gain, questions=questions, phone_ids=phone_ids if triphones else None,
-                      transitions=transitions)
     spk_of = lambda batch: [speaker_ids[items[i]["entry"][0]] for i in batch] if fmllr else None    # noqa: E731
-    history = aligner.fit([p[:3] for p in packed], iters, [spk_of(p[3]) for p in packed] if fmllr else None)
+    history = []
+    if aligner is None:
+        aligner = Aligner(len(phone_ids) * states, D, states, dev, mixtures, mix_iters, lda=lda, splice=splice, lda_iters=lda_iters,
+                          fmllr=fmllr, fmllr_rounds=fmllr_rounds, fmllr_iters=fmllr_iters, fmllr_sweeps=fmllr_sweeps,
+                          fmllr_min_frames=fmllr_min_frames, triphones=triphones, tri_iters=tri_iters, tri_min_occ=tri_min_occ,
+                          tri_min_gain=tri_min_gain, questions=questions, phone_ids=phone_ids if triphones else None,
+                          transitions=transitions)
+        history = aligner.fit([p[:3] for p in packed], iters, [spk_of(p[3]) for p in packed] if fmllr else None)
 
     written = 0
     phone_names = sorted(phone_ids, key=phone_ids.get)
+    heard = []                                                             # per utterance, the phones of the blocks with frames
     none_if_nan = lambda v: None if v != v else float(v)                                 # noqa: E731
     sink = open(scores, "w", encoding="utf-8") if scores is not None else None
     try:
@@ -2205,6 +2338,8 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
                 wd, ph, xmax = intervals(items[i]["graph"], items[i]["words"], fr, hop, sr)
                 write_textgrid(tg(e), wd, ph, xmax)
                 written += 1
+                if save_model is not None:
+                    heard.append(block_phones(items[i]["graph"])[np.nonzero(fr)[0]])
                 if sink is not None:
                     rows = sc["blocks"][np.nonzero(fr)[0]]                 # the written intervals: the blocks with frames
                     line = {"speaker": e[0], "basename": e[1], **{k: sc[k] for k in ("frames", "scored_frames", "viterbi", "loglik", "gop", "match")},
@@ -2217,4 +2352,8 @@ def build(config, device="cuda", states=2, iters=12, overwrite=False, batch_byte
     finally:
         if sink is not None:
             sink.close()
+    if save_model is not None:
+        from .recognize import feature_config, phone_bigram
+        aligner.save(save_model, phone_names, feature_config(config), speakers[:aligner.n_spk] if fmllr else None,
+                     phone_bigram(heard, len(phone_names))[0])
     return written, skipped, history

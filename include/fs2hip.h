@@ -554,6 +554,26 @@ int fs2_align_segment_scores(const double* f, long ldf_b, long ldf_t, const int3
                              const int32_t* cand, long ldc_b, long ldc_k, const double* w, const double* mu, const double* var,
                              int n_classes, int M, int D, const double* arc, double* ws, long ws_doubles, double* V, long ldv_b,
                              long ldv_k, int B, int Tmax, int Kmax, int P, int S, fs2_stream_t stream);
+/* Phone-loop recognition (csrc/fs2_align_loop.hip; specification: fastspeech2_amd/recognize.py).  No atomics.  P phones of S states,
+ * state j = p S + s is emission class j, C = P S; E [B][Tmax][>= C] from fs2_align_emit / fs2_align_emit_gmm with sid = 0 .. C - 1.
+ * Costs, fp64, finite or -inf: self_[C]; next_[C], the arc s - 1 -> s (unused at s = 0); link[p][q] (row stride ldl >= P), leave the
+ * last state of p and enter the first state of q; init[P]; final_[P].  The largest P (253: the backpointer is one byte). */
+int fs2_align_max_loop_phones(void);
+/* d[0][q S] = init[q] + E[0][q S], every other state -inf;  d[t][j] = E[t][j] + the maximum over, in code order, 0: d[t-1][j] +
+ * self_[j]; for s > 0, 1: d[t-1][j-1] + next_[j]; for s = 0, 2 + p: d[t-1][p S + S - 1] + link[p][q], p ascending; a later candidate
+ * replaces an earlier one only when strictly larger.  bp[b][t][j] (bytes, strides ldp_b >= Tmax ldp_t, ldp_t >= C) is the winning
+ * code, row 0 is 0.  end[b] = the state p S + S - 1 of the largest d[T-1][p S + S - 1] + final_[p], p ascending, strictly larger
+ * replaces; score[b] that value; end = -1 and score = -inf when it is -inf or lens[b] = 0.  Only adds and compares: exact.
+ * Nothing at t >= lens[b] is read or written.  FS2_EINVAL before any launch: P outside 1..fs2_align_max_loop_phones(), S outside
+ * 1..3, P S above fs2_align_max_states(), a bad stride, a null pointer. */
+int fs2_align_loop_viterbi(const double* E, long lde_b, long lde_t, const int32_t* lens, const double* self_, const double* next_,
+                           const double* link, long ldl, const double* init, const double* final_, uint8_t* bp, long ldp_b,
+                           long ldp_t, int32_t* end, double* score, int B, int Tmax, int P, int S, fs2_stream_t stream);
+/* The segments of the best path in time order: seg_phone[b][k] the phone, seg_start[b][k] the first frame (int32, row stride lds_b >=
+ * Tmax), n_seg[b] <= lens[b] of them; 0 when end[b] < 0 or lens[b] = 0.  A chain that leaves the table stops: n_seg = -1 and no
+ * segment is written.  Nothing at k >= n_seg[b] is written. */
+int fs2_align_loop_backtrack(const uint8_t* bp, long ldp_b, long ldp_t, const int32_t* lens, const int32_t* end, int32_t* seg_phone,
+                             int32_t* seg_start, long lds_b, int32_t* n_seg, int B, int Tmax, int P, int S, fs2_stream_t stream);
 /* The LDA stage (csrc/fs2_align_lda.hip).  Spliced frames y [B][Tmax][D_s], D_s = n_mel (2 c + 1), strides ldy_b >= Tmax ldy_t,
  * ldy_t >= D_s, in elements.  Limits, all FS2_EINVAL before any launch: 0 <= c <= 4, 1 <= k <= D_s <= fs2_align_max_splice_dim() (720).
  * Nothing at t >= lens[b] is read or written.  No atomics. */
