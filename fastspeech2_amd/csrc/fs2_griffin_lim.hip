@@ -50,13 +50,13 @@ extern "C" int fs2_gl_mel_to_mag(const float* mel, long sb, long sj, long st, co
 
 // ------------------------------------------------------------------ [m cos(phi) ; m sin(phi)] (stft.py:84-86)
 // Strided magnitude / phase (element (b, f, k) at b*sb + f*sf + k*sk): the reference's (B, NF, F) tensors as well as the loop's
-// frame-major magnitude.  One thread per G column.
+// frame-major magnitude.  One thread per G column; the row is grid x (B * Fmax passes the 65535 of grid y at a synthesis batch).
 __global__ void gl_recombine_kernel(const float* __restrict__ mag, long msb, long msf, long msk, const float* __restrict__ ph,
                                     long psb, long psf, long psk, const int32_t* __restrict__ frames, float* __restrict__ G,
                                     long ldg, int Fmax, int NF) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y * blockDim.x + threadIdx.x;
     if (c >= ldg) return;
-    const int row = blockIdx.y, b = row / Fmax, f = row - b * Fmax;
+    const int row = blockIdx.x, b = row / Fmax, f = row - b * Fmax;
     float v = 0.f;
     if (f < gl_frames(frames, b, Fmax) && c < 2 * NF) {
         const int k = c < NF ? c : c - NF;
@@ -71,7 +71,7 @@ extern "C" int fs2_gl_recombine(const float* mag, long msb, long msf, long msk, 
     FS2_CHECK_ARG(mag && phase && G, "gl_recombine: null pointer");
     FS2_CHECK_ARG(B >= 0 && Fmax > 0 && NF > 0 && ldg >= 2L * NF, "gl_recombine: bad shape B=%d Fmax=%d NF=%d ldg=%ld", B, Fmax, NF, ldg);
     if (B == 0) return FS2_OK;
-    gl_recombine_kernel<<<dim3(fs2_cdiv(ldg, 256), B * Fmax), 256, 0, stream>>>(mag, msb, msf, msk, phase, psb, psf, psk, frames, G,
+    gl_recombine_kernel<<<dim3(B * Fmax, fs2_cdiv(ldg, 256)), 256, 0, stream>>>(mag, msb, msf, msk, phase, psb, psf, psk, frames, G,
                                                                                ldg, Fmax, NF);
     FS2_CHECK_LAUNCH("gl_recombine");
     return FS2_OK;
@@ -83,10 +83,10 @@ extern "C" int fs2_gl_recombine(const float* mag, long msb, long msf, long msk, 
 // past NF zero the padding columns [2 NF, ldg).
 __global__ void gl_project_kernel(const float* __restrict__ ft, long ldft, int S, const float* __restrict__ mag, long msb, long msf,
                                   long msk, const int32_t* __restrict__ frames, float* __restrict__ G, long ldg, int Fmax, int NF) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.y * blockDim.x + threadIdx.x;
     const int npad = (int)(ldg - 2L * NF);
     if (k >= NF + npad) return;
-    const int row = blockIdx.y, b = row / Fmax, f = row - b * Fmax;
+    const int row = blockIdx.x, b = row / Fmax, f = row - b * Fmax;
     float* g = G + (size_t)row * ldg;
     if (k >= NF) { g[NF + k] = 0.f; return; }
     float vr = 0.f, vi = 0.f;
@@ -107,7 +107,7 @@ extern "C" int fs2_gl_project(const float* ft, long ldft, int S, const float* ma
                   "gl_project: bad shape B=%d Fmax=%d S=%d NF=%d ldft=%ld ldg=%ld", B, Fmax, S, NF, ldft, ldg);
     if (B == 0) return FS2_OK;
     const long nthr = ldg - NF;
-    gl_project_kernel<<<dim3(fs2_cdiv(nthr, 256), B * Fmax), 256, 0, stream>>>(ft, ldft, S, mag, msb, msf, msk, frames, G, ldg, Fmax, NF);
+    gl_project_kernel<<<dim3(B * Fmax, fs2_cdiv(nthr, 256)), 256, 0, stream>>>(ft, ldft, S, mag, msb, msf, msk, frames, G, ldg, Fmax, NF);
     FS2_CHECK_LAUNCH("gl_project");
     return FS2_OK;
 }
@@ -175,9 +175,9 @@ extern "C" int fs2_gl_ola(const float* seg, long lds, const int32_t* frames, con
 // phase = atan2(im, re); both (B, NF, F) channel-major like the reference.
 __global__ void gl_mag_phase_kernel(const float* __restrict__ ft, long ldft, int S, float* __restrict__ mag, float* __restrict__ phase,
                                     int F, int NF) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.y * blockDim.x + threadIdx.x;
     if (k >= NF) return;
-    const int f = blockIdx.y, b = blockIdx.z;
+    const int f = blockIdx.x, b = blockIdx.z;
     const float* r = ft + ((size_t)b * S + f) * ldft;
     const float re = r[k], im = r[NF + k];
     const size_t o = ((size_t)b * NF + k) * F + f;
@@ -188,7 +188,7 @@ extern "C" int fs2_gl_mag_phase(const float* ft, long ldft, int S, float* mag, f
     FS2_CHECK_ARG(ft && mag && phase, "gl_mag_phase: null pointer");
     FS2_CHECK_ARG(B >= 0 && F > 0 && S >= F && NF > 0 && ldft >= 2L * NF, "gl_mag_phase: bad shape B=%d F=%d S=%d NF=%d", B, F, S, NF);
     if (B == 0) return FS2_OK;
-    gl_mag_phase_kernel<<<dim3(fs2_cdiv(NF, 256), F, B), 256, 0, stream>>>(ft, ldft, S, mag, phase, F, NF);
+    gl_mag_phase_kernel<<<dim3(F, fs2_cdiv(NF, 256), B), 256, 0, stream>>>(ft, ldft, S, mag, phase, F, NF);
     FS2_CHECK_LAUNCH("gl_mag_phase");
     return FS2_OK;
 }

@@ -76,3 +76,71 @@ def test_too_short_is_rejected_before_any_device_call(tmp_path):
     assert not (tmp_path / "x.wav").exists()
     with pytest.raises(RuntimeError, match="AMD GPU only"):                     # long enough: CPU tensors are refused
         griffin_lim(torch.zeros(1, 513, 4), stft.stft_fn, 2)
+
+
+# ---------------------------------------------------------------------------------------------- the per-kernel oracle
+@pytest.mark.parametrize("setting", [(256, 64, 200), (1024, 256, 1024)])
+def test_kernel_contracts_compose_to_the_reference_functions(setting):
+    """ola(recombine(...) @ inverse_basis) is STFT.inverse and mag_phase(frames @ forward_basis^T) is STFT.transform, in fp64"""
+    filt, hop, win = setting
+    s = gl_ref.STFT(filt, hop, win)
+    rng = np.random.RandomState(filt + win)
+    B, F, NF = 2, 9, filt // 2 + 1
+    mag, ph = np.exp(rng.standard_normal((B, NF, F))), rng.uniform(-np.pi, np.pi, (B, NF, F))
+    want = s.inverse(mag, ph)
+    G = gl_ref.recombine(mag.transpose(0, 2, 1), ph.transpose(0, 2, 1), ldg=2 * NF + 2)
+    assert not G[..., 2 * NF:].any()
+    N = hop * (F - 1)
+    xp, y = gl_ref.ola(G[..., :2 * NF] @ s.inverse_basis, None, gl_ref.window(win, filt) ** 2, filt, hop, N + filt + 3, N + 2)
+    assert np.abs(y[:, :N] - want).max() <= 1e-12 * np.abs(want).max() and not y[:, N:].any()
+    assert np.array_equal(xp[:, :N + filt], np.pad(y[:, :N], ((0, 0), (filt // 2, filt // 2)), mode="reflect")) and not xp[:, N + filt:].any()
+    x = rng.standard_normal((B, N))
+    wm, wp = s.transform(x)
+    gm, gp = gl_ref.mag_phase(s.frames_of(x) @ s.forward_basis.T)
+    assert gm.shape == wm.shape == (B, NF, F)
+    assert np.abs(gm - wm).max() <= 1e-12 * np.abs(wm).max() and np.abs(gp - wp).max() <= 1e-12 * np.pi
+    # project = recombine of the transform's phase, and ragged rows are zero whatever lies there
+    ft = s.frames_of(x) @ s.forward_basis.T
+    m = mag.transpose(0, 2, 1)
+    assert np.array_equal(gl_ref.project(ft, m), gl_ref.recombine(m, gp.transpose(0, 2, 1)))
+    poisoned = m.copy()
+    poisoned[1, 4:] = np.nan
+    Gr = gl_ref.project(ft, poisoned, frames=[F + 3, 4])
+    assert np.array_equal(Gr[0], gl_ref.project(ft, m)[0]) and np.array_equal(Gr[1, :4], gl_ref.project(ft, m)[1, :4]) and not Gr[1, 4:].any()
+    # the float32 evaluation: the reference's casts, a float32 result, within float32 rounding of the fp64 one
+    s32 = gl_ref.STFT(filt, hop, win, dtype=np.float32)
+    assert s32.forward_basis.dtype == s32.inverse_basis.dtype == np.float32
+    y32 = s32.inverse(mag, ph)
+    m32, _ = s32.transform(x)
+    assert y32.dtype == m32.dtype == np.float32 and y32.shape == want.shape and m32.shape == wm.shape
+    assert 0 < np.abs(y32 - want).max() <= 1e-4 * np.abs(want).max() and 0 < np.abs(m32 - wm).max() <= 1e-4 * np.abs(wm).max()
+
+
+def test_float32_envelope_of_the_oracle_is_the_hosts():
+    """gl_ref.ola in float32 divides by the envelope audio.window_sumsquare builds (given the same window), bit for bit"""
+    from fastspeech2_amd.audio import _window, window_sumsquare
+    for filt, hop, win in [(1024, 256, 256), (256, 64, 200), (64, 64, 64)]:
+        F = 7
+        w2 = _window("hann", win, filt) ** 2
+        env = window_sumsquare("hann", F, hop, win, filt)
+        N = hop * (F - 1)
+        _, y = gl_ref.ola(np.ones((1, F, filt), np.float32), None, w2, filt, hop, 0, N, dtype=np.float32)
+        count = np.zeros(N + filt, np.float32)
+        for f in range(F):
+            count[f * hop:f * hop + filt] += 1
+        want = np.where(env > gl_ref.TINY32, count / np.where(env > gl_ref.TINY32, env, 1), count) * np.float32(filt / hop)
+        assert y.dtype == want.dtype == np.float32 and np.array_equal(y[0], want[filt // 2:filt // 2 + N])
+        assert win == filt or (env == 0).any()                     # a zero-padded window: the envelope reaches exact zeros
+
+
+def test_kernel_bars_are_what_the_generator_writes():
+    from tests import gl_cases
+    rec, now = gl_cases.bars(), gl_cases.measure()
+    assert rec == now, {k: (rec.get(k), now.get(k)) for k in set(rec) | set(now) if rec.get(k) != now.get(k)}
+    assert rec["factor"] == 4
+    n = 0
+    for group in ("mag_rel", "phase", "recombine", "project", "ola"):
+        for key, bar in rec[group].items():
+            assert np.isfinite(bar) and 0 < bar < 1e-5, (group, key, bar)          # a few float32 roundings, in every normalisation
+            n += 1
+    assert n == 4 * 4 + len(gl_cases.OLA_SETTINGS)

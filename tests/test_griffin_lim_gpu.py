@@ -1,7 +1,9 @@
 """Griffin-Lim mel inversion on the GPU (fastspeech2_amd.audio STFT / griffin_lim / inv_mel_spec / mels_to_wavs_griffin_lim,
 csrc/fs2_griffin_lim.hip + the fp32 framed-DFT GEMMs) against the live reference's fp32 results (tests/golden/griffin_lim.npz,
 per-quantity bars = 4 x the reference's own distance from an fp64 evaluation), the ragged batch against its utterances
-alone, and synthesize.py --griffin_iters."""
+alone, and synthesize.py --griffin_iters.  All of it at the production STFT (filter 1024, hop 256, window 1024) and through the
+whole pipeline; each kernel alone against fp64, the other STFT sizes, the ragged edges and row counts above 65 535 are
+tests/test_griffin_lim_kernels_gpu.py."""
 import os
 
 import numpy as np
