@@ -633,12 +633,18 @@ class _Rates:
 
 
 def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=None, score_fn=None,
-        device="cuda", cepstra="mel", alpha=None, prosody=False, f0_estimator="dio"):
+        device="cuda", cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", aligned=False, max_len_diff=None, aligned_fn=None):
     """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
     replaces the device stage (called with `prosody=True` as a keyword when that is asked for).  Returns (rows, skipped, summary).
     With cepstra="world" the rows and the summary also say cepstra, alpha and fft_size; with "mel" they are what they were before
     that choice existed.  `prosody` adds the prosody keys of the module docstring and is refused with f0=False before a file is
-    read.  `f0_estimator` "pyin" (score.py --f0 pyin) scores F0 and prosody on pYIN tracks: rows and summary then say f0_estimator."""
+    read.  `f0_estimator` "pyin" (score.py --f0 pyin) scores F0 and prosody on pYIN tracks: rows and summary then say f0_estimator.
+    `aligned` (score.py --aligned) is for wavs that share the recording's time axis, copysynth.py's: a pair whose two lengths differ
+    by more than `max_len_diff` samples (default 2 hop_length, a choice: a copy-synthesis wav is T hop long, within one hop of the
+    TextGrid window) is skipped as "not time-aligned"; every other pair, cut to its shorter side, also gets stoi, estoi,
+    stoi_frames_kept, stoi_segments and aligned_samples (`stoi`), and the summary their means over the rows that are not too short
+    and the number of those that are.  `aligned_fn(ref_wavs, syn_wavs) -> [dict]` replaces that device stage.  Without `aligned`
+    every row, every summary key and every launch is what it is without this paragraph."""
     import json
     pp = config["preprocessing"]
     sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
@@ -653,7 +659,21 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
         world_keys = {"cepstra": "world", "alpha": Env.alpha_for(sr, alpha), "fft_size": Env.fft_size(sr)}
     elif cepstra != "mel" or alpha is not None:
         raise ValueError(f"cepstra must be 'mel' (without alpha) or 'world', got {cepstra!r}, alpha={alpha}")
+    if aligned:
+        max_len_diff = 2 * hop if max_len_diff is None else max_len_diff
+        if int(max_len_diff) != max_len_diff or max_len_diff < 0:
+            raise ValueError(f"max_len_diff must be a number of samples >= 0, got {max_len_diff!r}")
     items, skipped = collect(config, result_path, source, syn_dir, ref_dir, trim)
+    if aligned:
+        kept = []
+        for it in items:
+            diff = abs(len(it["ref"]) - len(it["syn"]))
+            if diff > max_len_diff:
+                skipped.append((it["basename"], f"not time-aligned: the reference has {len(it['ref'])} samples, the synthesized file "
+                                                f"{len(it['syn'])}, {diff} apart (more than {int(max_len_diff)})"))
+            else:
+                kept.append(it)
+        items = kept
     if score_fn is None:
         from . import audio as Audio
         stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], pp["mel"]["n_mel_channels"], sr,
@@ -666,12 +686,22 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
     scores = score_fn([it["ref"] for it in items], [it["syn"] for it in items]) if items else []
     rows = [{"basename": it["basename"], "speaker": it["speaker"], "reference_window": it["window"], **sc}
             for it, sc in zip(items, scores)]
+    if aligned:
+        from . import stoi as Stoi
+        if aligned_fn is None:
+            aligned_fn = lambda r, s: Stoi.score_pairs(r, s, sr, device=device)   # noqa: E731
+        cut = [min(len(it["ref"]), len(it["syn"])) for it in items]
+        more = aligned_fn([it["ref"][:n] for it, n in zip(items, cut)], [it["syn"][:n] for it, n in zip(items, cut)]) if items else []
+        for row, sc in zip(rows, more):
+            row.update(sc)
     if out_path:
         with open(out_path, "w", encoding="utf-8") as f:
             for row in rows:
                 f.write(json.dumps(row) + "\n")
     summary = summarize(rows)
     summary.update(world_keys)
+    if aligned:
+        summary.update(Stoi.summarize(rows))
     if f0 and f0_estimator != "dio":
         summary["f0_estimator"] = f0_estimator
     summary["skipped"] = len(skipped)

@@ -680,6 +680,38 @@ int fs2_dtw_prosody(const int32_t* pi, const int32_t* pj, long ldq, const int32_
 int fs2_prosody_voiced(const double* f0, long ldf, const int32_t* lens, double* out, long ldo, int32_t* nv, double* stats, long lds,
                        int B, int Tmax, fs2_stream_t stream);
 
+/* ---- time-aligned intelligibility: STOI and ESTOI (csrc/fs2_stoi.hip; specification: fastspeech2_amd/stoi.py) ----
+ * Ragged batches of time-aligned pairs at 10 kHz: float32 rows x (clean) and y (B, ldx) sharing one device lens, fp64 after the load,
+ * no atomics, fixed-order sums: the same input gives the same bytes.  Nothing at or beyond lens[b] is read.  Frames of 256 samples at
+ * hop 128 start at s = 0, 128, .. with s < len - 256: F(len) = ceil((len - 256) / 128) for len > 256, else 0; Fmax = F(Nmax).  w [256]
+ * is the caller's window.  Buffers of Fmax = 0 frames may be NULL.
+ * fs2_stoi_frame_energy: e[b][j] = sum_n (x[b][128 j + n] w[n])^2, j < F(lens[b]). */
+int fs2_stoi_frame_energy(const float* x, long ldx, const int32_t* lens, const double* w, double* e, long lde, int B, int Nmax,
+                          fs2_stream_t stream);
+/* mask[b][j] = (max_j e > 0 and e[b][j] > 1e-4 max_j e), j < F(lens[b]); map[b][i] = the i-th frame with mask 1, i < n_kept[b]
+ * (int32 rows of stride ldm >= Fmax; nothing beyond those counts is written) */
+int fs2_stoi_keep(const double* e, long lde, const int32_t* lens, int32_t* mask, int32_t* map, long ldm, int32_t* n_kept, int B,
+                  int Nmax, fs2_stream_t stream);
+/* xo[b][128 i + n] = sum over the kept frames i that cover the sample, ascending, of x[b][128 map[b][i] + n] w[n], and yo of y the
+ * same: (n_kept[b] - 1) 128 + 256 samples per row (none when n_kept[b] = 0), ldo >= (Fmax - 1) 128 + 256; a gather, nothing is
+ * scattered.  A map entry outside [0, F) is clamped into it. */
+int fs2_stoi_ola(const float* x, const float* y, long ldx, const int32_t* lens, const double* w, const int32_t* map, long ldm,
+                 const int32_t* n_kept, double* xo, double* yo, long ldo, int B, int Nmax, fs2_stream_t stream);
+/* X[b][k][m] = sqrt(sum of |DFT_512(xo[b][128 m .. 128 m + 256) w)|^2 over the bins [edges[k], edges[k + 1])), k < 15, m < n_kept[b] - 1
+ * (strides ldx_b >= 15 ldx_k, ldx_k >= Fmax - 1).  twiddle [512][2] = {cos, sin}(2 pi j / 512) is the caller's device table: no sine
+ * is evaluated here.  edges: HOST memory, 16 ascending bins within [0, 257] spanning at most 256. */
+int fs2_stoi_bands(const double* xo, long ldo, const int32_t* n_kept, const double* w, const double* twiddle, const int32_t* edges,
+                   double* X, long ldx_b, long ldx_k, int B, int Fmax, fs2_stream_t stream);
+/* Per segment s < n_kept[b] - 30 of 30 frames of X and Y (both as fs2_stoi_bands writes them): seg[b][0][s] = the mean over the 15
+ * bands of the STOI correlation (clip = 1 + 10^(15 / 20) bounds alpha Y by clip X), seg[b][1][s] = the ESTOI score (rows, then
+ * columns normalised; sum / 30); strides lds_b >= 2 lds_k, lds_k >= Fmax - 30 */
+int fs2_stoi_segments(const double* X, const double* Y, long ld_b, long ld_k, const int32_t* n_kept, double clip, double* seg,
+                      long lds_b, long lds_k, int B, int Fmax, fs2_stream_t stream);
+/* out[b][6] = {STOI, ESTOI (the means of the row's S = max(n_kept[b] - 30, 0) segment scores in a fixed order; NaN when S = 0),
+ * F(lens[b]), n_kept[b], S, S == 0} */
+int fs2_stoi_mean(const double* seg, long lds_b, long lds_k, const int32_t* lens, const int32_t* n_kept, double* out, int B, int Nmax,
+                  fs2_stream_t stream);
+
 /* ---- spectral envelope (CheapTrick) and its mel-cepstrum (specification: fastspeech2_amd/envelope.py) ----
  * fp64 throughout, ragged: row b has lens[b] samples of the float32 batch x (row stride ldx) and frames[b] frames (int32, device);
  * f0 [B][ldf] f64, one value per frame; spectra [B][Fmax][N / 2 + 1] with batch / frame strides in elements, N a power of two in

@@ -2,7 +2,8 @@
 """score.py — objective scores of synthesized against recorded speech on the GPU (fastspeech2_amd/metrics.py):
 
     python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
-                    [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--f0 {dio,pyin}] [--out scores.jsonl]
+                    [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--f0 {dio,pyin}] [--aligned] [--max_len_diff N]
+                    [--out scores.jsonl]
 
 For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
 is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
@@ -18,7 +19,11 @@ gross pitch error, F0 frame error and log-F0 correlation on the path, the DTW di
 mean absolute error of the frame energy, and the standard deviation, skewness and excess kurtosis of the voiced F0 of both sides.
 The paper does not say how it treats unvoiced frames or in which unit its DTW distance is: these compare runs of this tool.
 With `--f0 pyin` both sides of every F0 and prosody number come from probabilistic YIN (fastspeech2_amd/pyin.py) instead of DIO +
-StoneMask, an independent estimator to cross-check the pitch scores with; rows and summary then carry `f0_estimator`."""
+StoneMask, an independent estimator to cross-check the pitch scores with; rows and summary then carry `f0_estimator`.
+With `--aligned` the synthesized wavs are taken to share the recording's time axis, as copysynth.py's do (a recorded mel through the
+vocoder): a pair whose lengths differ by more than `--max_len_diff` samples (default 2 hop_length) is skipped as not time-aligned,
+every other pair is cut to its shorter side and also gets STOI and ESTOI (fastspeech2_amd/stoi.py: the published algorithms on this
+project's own resampler; agreement with pystoi or the authors' MATLAB code is unmeasured), and the summary their corpus means."""
 import argparse
 import json
 import sys
@@ -46,12 +51,16 @@ def parse_args(argv=None):
     parser.add_argument("--f0", choices=("dio", "pyin"), default="dio",
                         help="estimator of both sides of every F0 and prosody score: DIO + StoneMask or probabilistic YIN; with --cepstra "
                              "world CheapTrick keeps its own DIO + StoneMask F0 whatever this says")
+    parser.add_argument("--aligned", action="store_true",
+                        help="the wavs are sample-aligned with the recordings (copysynth.py): also STOI and ESTOI per pair")
+    parser.add_argument("--max_len_diff", type=int, default=None,
+                        help="--aligned: skip a pair whose lengths differ by more samples than this (default 2 hop_length)")
     parser.add_argument("--out", type=str, default="scores.jsonl")
     parser.add_argument("--device", type=str, default="cuda")
     return parser.parse_args(argv)
 
 
-def main(argv=None, score_fn=None):
+def main(argv=None, score_fn=None, aligned_fn=None):
     args = parse_args(argv)
     config = yaml.load(open(args.preprocess_config, "r"), Loader=yaml.FullLoader)
     train = yaml.load(open(args.train_config, "r"), Loader=yaml.FullLoader)
@@ -59,7 +68,8 @@ def main(argv=None, score_fn=None):
         rows, skipped, summary = metrics.run(config, train["path"]["result_path"], args.source, out_path=args.out, syn_dir=args.syn_dir,
                                              ref_dir=args.ref_dir, trim=not args.no_trim, f0=not args.no_f0, n_mcep=args.n_mcep,
                                              score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha,
-                                             prosody=args.prosody, f0_estimator=args.f0)
+                                             prosody=args.prosody, f0_estimator=args.f0, aligned=args.aligned,
+                                             max_len_diff=args.max_len_diff, aligned_fn=aligned_fn)
     except ValueError as e:
         sys.exit(str(e))
     for name, reason in skipped:
