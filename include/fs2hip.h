@@ -712,6 +712,44 @@ int fs2_stoi_segments(const double* X, const double* Y, long ld_b, long ld_k, co
 int fs2_stoi_mean(const double* seg, long lds_b, long lds_k, const int32_t* lens, const int32_t* n_kept, double* out, int B, int Nmax,
                   fs2_stream_t stream);
 
+/* ---- speaker similarity: GMM-UBM (csrc/fs2_spk.hip; specification: fastspeech2_amd/speaker.py) ----
+ * fp64 throughout, no atomics, fixed-order sums: the same input gives the same bytes.  Frames are PACKED: utterance u owns the rows
+ * offs[u] .. offs[u] + n_kept[u] of a [N][D] matrix (offs, n_kept: int32 on the device).  A mixture is given expanded: a[m][d] =
+ * mu / var, b[m][d] = -1 / (2 var) (rows of stride ldt >= D), c[m] = log w - 1/2 sum_d (log(2 pi var) + mu^2 / var), -inf allowed;
+ * L[n][m] = c[m] + sum_d (x[n][d] a[m][d] + x[n][d]^2 b[m][d]).  Limits, all FS2_EINVAL before any launch: 1 <= D <=
+ * fs2_spk_max_dim() (64), 1 <= M <= fs2_spk_max_components() (2048), G M < 2^31, N < 2^31 (an int).  Nothing beyond a row's D columns
+ * or at a row >= N is read or written. */
+int fs2_spk_max_dim(void);
+int fs2_spk_max_components(void);
+/* cep [B][Tmax][n_cep + 1] (strides ldc_b >= Tmax ldc_t, ldc_t >= n_cep + 1; column 0 is c0), 1 <= n_cep <= 32, D = 2 n_cep.  Feature j
+ * of frame t: cepstrum j + 1 for j < n_cep, else (d1 + 2 d2) / 10 with dk = c[min(t + k, T - 1)] - c[max(t - k, 0)] of cepstrum
+ * j - n_cep + 1.  A frame passes when c0[t] >= max_t c0 - energy_floor (>= 0).  With n >= 2 frames passing: mean[b][j] = their sum in
+ * ascending t over n, var[b][j] = the sum of the squared differences from that mean over n (rows of stride ldm >= D); when every var is
+ * > 0, n_kept[b] = n and feat[offs[b] + i][j] = (f - mean) / sqrt(var) for the i-th passing frame (row stride ldf >= D), else n_kept[b]
+ * = 0 and no row is written.  With n < 2: n_kept[b] = 0, mean and var NaN, no row written.  Nothing at t >= lens[b] is read; rows
+ * beyond n_kept[b] are not written.  One workgroup per utterance. */
+int fs2_spk_feats(const double* cep, long ldc_b, long ldc_t, const int32_t* lens, const int32_t* offs, int n_cep, double energy_floor,
+                  double* feat, long ldf, int32_t* n_kept, double* mean, double* var, long ldm, int B, int Tmax, fs2_stream_t stream);
+/* lse[n][g] = log sum_m exp L[n][g M + m] for the G groups of M components in a, b [G M][ldt], c [G M] (row stride ldl >= G); -inf when
+ * every c of the group is -inf.  post, NULL or for G = 1 only: post[n][m] = exp(L[n][m] - lse[n]) (row stride ldp >= M), 0 where lse
+ * is -inf.  The contraction runs on v_mfma_f64_16x16x4_f64 over k = (x, x^2), four k per step ascending; a workgroup owns 64 frames
+ * and walks the 64-component tiles of its groups, folding them into a running (max, sum) in a fixed order. */
+int fs2_spk_loglik(const double* x, long ldx, const double* a, const double* b, long ldt, const double* c, double* lse, long ldl,
+                   double* post, long ldp, int N, int D, int M, int G, fs2_stream_t stream);
+/* doubles of workspace fs2_spk_accum needs (0 for N <= 0 or D, M outside their limits): chunks x ceil(M / 64) x ceil((1 + 2 D) / 64)
+ * tiles of 4096, at most 32 x 32 x 3 of them */
+int fs2_spk_accum_ws(int N, int D, int M);
+/* stats[m][0 .. 1 + 2 D) += sum_n post[n][m] (1, x[n][0..D), x[n][0..D)^2) (row stride lds >= 1 + 2 D); the caller zeroes stats before
+ * the first batch.  The N rows are cut into at most 32 chunks whose length (a multiple of 16) depends on N only; 64 x 64 tiles are
+ * summed per chunk with v_mfma_f64_16x16x4_f64 in ascending n into ws and added in ascending chunk order.  ws_doubles below
+ * fs2_spk_accum_ws() is FS2_EINVAL. */
+int fs2_spk_accum(const double* post, long ldp, const double* x, long ldx, double* stats, long lds, double* ws, long ws_doubles, int N,
+                  int D, int M, fs2_stream_t stream);
+/* out[u][g] = (sum over r = offs[u] .. offs[u] + n_kept[u], ascending, of lse[r][g] - ubm[r]) / n_kept[u], g < G (row strides ldl,
+ * ldo >= G); NaN when n_kept[u] <= 0.  IEEE arithmetic on -inf: a -inf in lse alone gives -inf, in both gives NaN. */
+int fs2_spk_mean_rows(const double* lse, long ldl, const double* ubm, const int32_t* offs, const int32_t* n_kept, double* out, long ldo,
+                      int U, int G, fs2_stream_t stream);
+
 /* ---- spectral envelope (CheapTrick) and its mel-cepstrum (specification: fastspeech2_amd/envelope.py) ----
  * fp64 throughout, ragged: row b has lens[b] samples of the float32 batch x (row stride ldx) and frames[b] frames (int32, device);
  * f0 [B][ldf] f64, one value per frame; spectra [B][Fmax][N / 2 + 1] with batch / frame strides in elements, N a power of two in
