@@ -70,6 +70,12 @@ All arithmetic is float64, sums are in a fixed order without atomics, padding is
   and kurtosis also where sigma = 0).
 Without `prosody` every row and every summary key is what it is without this section.
 
+Over-smoothing (`smoothing=True`, `score.py --smoothing`).  The global variance and the modulation spectrum of both sides' cepstra,
+per utterance and off the path, specified in full in the docstring of `modspec`: every row also carries gv_ref, gv_syn,
+gv_ratio_db, ms_db_ref, ms_db_syn, ms_band_db_ref, ms_band_db_syn and ms_dist_db, the summary ms_bands_hz, ms_diff_db_by_band,
+ms_dist_db_corpus, gv_ratio_db_by_coef, the means gv_ratio_db_mean and ms_dist_db_mean with their `_nan_utterances` counts, and
+smoothing_too_short_utterances.  Without `smoothing` every launch, every row and the summary are what they are without this paragraph.
+
 Storage.  The local costs and backpointers of a pair are held skewed, cell (i, j) at row (i + j) mod T2, column i of a (T2max, T1max)
 matrix: an anti-diagonal is contiguous, the buffer is no larger than the plain one (`unskew` undoes it for a test).  The accumulated
 costs never leave the chip.  Determinism: no atomics, sums in a fixed order; two runs give byte-identical scores.
@@ -89,6 +95,7 @@ CELL_BYTES = 9                                              # one float64 local 
 PROSODY_SUMS = 8                                            # gross, n, V/UV mismatches, Sxx, Syy, Sxy, sum |de|, sum e_ref
 PROSODY_FRAME_BYTES = 24                                    # per frame: the compacted contour (8 B) and its share of the second path
 CORR_FLOOR = 1e-24
+SMOOTHING_BANDS = 8                                         # at most: the bands of `modspec.EDGES_HZ`
 PROSODY_SCORES = ("gpe", "ffe", "f0_corr", "f0_dtw_hz", "energy_mae", "energy_mae_rel")
 
 
@@ -443,16 +450,21 @@ def summarize(rows):
         out["f0_nan_utterances"] = int((~ok).sum())
     if "gpe" in rows[0]:
         _summarize_prosody(rows, out)
+    if "gv_ratio_db" in rows[0]:
+        from . import modspec as Modspec
+        out.update(Modspec.summarize(rows))
     return out
 
 
-def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0, prosody=False):
+def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0, prosody=False, smoothing=False):
     """What a batch of n pairs padded to (T1, T2) frames holds on the device: 9 B per (i, j) cell (local cost + backpointer), the
     audio, its STFT workspace and mel (about 40 B per sample), cepstra, F0 and the path; with `fft_size` (cepstra="world") also the
     spectral envelope, fft_size / 2 + 1 float64 bins per frame and side; with `prosody` the compacted contours and the second path
-    (24 B per frame; the contour DTW's cells reuse the first DTW's, released by then)."""
+    (24 B per frame; the contour DTW's cells reuse the first DTW's, released by then); with `smoothing` the moments and band values
+    of both sides, (2 + SMOOTHING_BANDS) float64 per coefficient and side."""
     return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64 + (fft_size // 2 + 1) * 8 * (fft_size > 0)
-                                                    + PROSODY_FRAME_BYTES * bool(prosody)))
+                                                    + PROSODY_FRAME_BYTES * bool(prosody))
+                + 2 * n_mcep * (2 + SMOOTHING_BANDS) * 8 * bool(smoothing))
 
 
 def load_audio(path, sampling_rate):
@@ -473,7 +485,7 @@ def frame_counts(n_samples, sampling_rate, hop_length, f0=True):
 
 
 def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None, f0=True, device="cuda", budget=4 << 30,
-                cepstra="mel", alpha=None, prosody=False, f0_estimator="dio"):
+                cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", smoothing=False):
     """Scores of (recorded, synthesized) pairs of float32 waveforms at `sampling_rate` -> one dict per pair (module docstring), in
     the order given.  `stft` is the config's `audio.TacotronSTFT`.  Pairs are packed longest first into ragged batches under `budget`
     bytes of device buffers; per batch: both sides through one pinned staging buffer, mel -> cepstra -> local cost -> scan ->
@@ -487,8 +499,11 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
     every F0 and prosody score from probabilistic YIN (`pyin`, the same frame grid) instead of DIO + StoneMask, and every row then
     carries f0_estimator; with "dio" the rows are what they were before that choice existed.  CheapTrick (cepstra="world") keeps
     its own DIO + StoneMask track whatever the estimator.  The pYIN workspace of a batch (`pyin.workspace_bytes`) counts towards
-    `budget`."""
+    `budget`.  With `smoothing` the two kernels of `modspec` run on both sides' cepstra, whichever they are, before these are
+    released, their results ride in the batch's one D2H copy, and every row also carries the over-smoothing keys of the module
+    docstring."""
     from . import envelope as Env
+    from . import modspec as Modspec
     if f0_estimator not in ("dio", "pyin"):
         raise ValueError(f"f0_estimator must be 'dio' or 'pyin', got {f0_estimator!r}")
     if prosody and not f0:
@@ -517,6 +532,7 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
     fr = [frame_counts(len(w), sampling_rate, hop_length, f0 or world) for w in ref_wavs]
     fs = [frame_counts(len(w), sampling_rate, hop_length, f0 or world) for w in syn_wavs]
     check_frames(fr, fs)
+    bins = Modspec.band_bins(sampling_rate, hop_length)[0] if smoothing else None
     short = [] if world and not prosody else [len(w) for w in list(ref_wavs) + list(syn_wavs) if len(w) <= stft.filter_length // 2]
     if short:
         raise ValueError(f"a waveform of {short[0]} samples is too short for the STFT's reflect padding ({stft.filter_length // 2})")
@@ -544,7 +560,7 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
             return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), scored if f0 else None, energy
         return cepstra_fn(mel, frames, n_mcep), scored, energy
 
-    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody)     # noqa: E731
+    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody, smoothing)     # noqa: E731
     if f0 and f0_estimator == "pyin":                                       # one side's pYIN chunk workspace lives at a time
         from . import pyin as Pyin
         cepstral = cost
@@ -554,6 +570,7 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
         a, f0a, ea = side([ref_wavs[i] for i in batch], al)
         b, f0b, eb = side([syn_wavs[i] for i in batch], bl)
         total, plen, pi, pj = dtw(a, al, b, bl)
+        smooth = [v.reshape(len(batch), -1) for v in Modspec.measure(a, al, bins) + Modspec.measure(b, bl, bins)] if smoothing else []
         del a, b
         cols = [total, plen.to(torch.float64)]
         if f0:
@@ -565,12 +582,17 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
             w, nw, sw = voiced_contours(f0b, bl)
             ctotal, cplen, _, _, _ = contour_dtw(u, nu.cpu(), w, nw.cpu())    # the voiced counts: one small D2H copy per side
             cols += list(su.unbind(1)) + list(sw.unbind(1)) + [ctotal, cplen.to(torch.float64)]
-        host = torch.stack(cols, dim=1).cpu().numpy()                       # the batch's one D2H copy of the scores
+        n_cols = len(cols)
+        scores = torch.stack(cols, dim=1)
+        host = (torch.cat([scores] + smooth, dim=1) if smoothing else scores).cpu().numpy()     # the batch's one D2H copy of the scores
         for r, i in enumerate(batch):
             rows[i] = scores_from_sums(host[r, 0], host[r, 1], al[r], bl[r], host[r, 2:5] if f0 else None)
             if prosody:
-                q = host[r, 5:]
+                q = host[r, 5:n_cols]
                 rows[i].update(prosody_scores(q[:8], host[r, 1], q[8:13], q[13:18], q[18], q[19]))
+            if smoothing:
+                m2a, ba, m2b, bb = np.split(host[r, n_cols:], np.cumsum([n_mcep, n_mcep * len(bins), n_mcep])[:3])
+                rows[i].update(Modspec.row_scores(m2a, ba.reshape(n_mcep, -1), al[r], m2b, bb.reshape(n_mcep, -1), bl[r]))
             if world:
                 rows[i].update(cepstra="world", alpha=alpha, fft_size=fft_size)
             if f0 and f0_estimator != "dio":
@@ -633,7 +655,8 @@ class _Rates:
 
 
 def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=None, score_fn=None,
-        device="cuda", cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", aligned=False, max_len_diff=None, aligned_fn=None):
+        device="cuda", cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", aligned=False, max_len_diff=None, aligned_fn=None,
+        smoothing=False):
     """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
     replaces the device stage (called with `prosody=True` as a keyword when that is asked for).  Returns (rows, skipped, summary).
     With cepstra="world" the rows and the summary also say cepstra, alpha and fft_size; with "mel" they are what they were before
@@ -644,7 +667,9 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
     TextGrid window) is skipped as "not time-aligned"; every other pair, cut to its shorter side, also gets stoi, estoi,
     stoi_frames_kept, stoi_segments and aligned_samples (`stoi`), and the summary their means over the rows that are not too short
     and the number of those that are.  `aligned_fn(ref_wavs, syn_wavs) -> [dict]` replaces that device stage.  Without `aligned`
-    every row, every summary key and every launch is what it is without this paragraph."""
+    every row, every summary key and every launch is what it is without this paragraph.  `smoothing` (score.py --smoothing) adds
+    the over-smoothing keys of `modspec` to every row and to the summary, with ms_bands_hz, the band edges in Hz at this config's
+    frame rate; a `score_fn` is then called with `smoothing=True` as a keyword."""
     import json
     pp = config["preprocessing"]
     sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
@@ -679,10 +704,10 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
         stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], pp["mel"]["n_mel_channels"], sr,
                                   pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
         score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device, cepstra=cepstra,     # noqa: E731
-                                            alpha=alpha, prosody=prosody, f0_estimator=f0_estimator)
-    elif prosody:
-        given = score_fn
-        score_fn = lambda r, s: given(r, s, prosody=True)                    # noqa: E731
+                                            alpha=alpha, prosody=prosody, f0_estimator=f0_estimator, smoothing=smoothing)
+    elif prosody or smoothing:
+        given, asked = score_fn, {k: True for k, v in (("prosody", prosody), ("smoothing", smoothing)) if v}
+        score_fn = lambda r, s: given(r, s, **asked)                         # noqa: E731
     scores = score_fn([it["ref"] for it in items], [it["syn"] for it in items]) if items else []
     rows = [{"basename": it["basename"], "speaker": it["speaker"], "reference_window": it["window"], **sc}
             for it, sc in zip(items, scores)]
@@ -702,6 +727,9 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
     summary.update(world_keys)
     if aligned:
         summary.update(Stoi.summarize(rows))
+    if smoothing:
+        from . import modspec as Modspec
+        summary["ms_bands_hz"] = [list(b) for b in Modspec.band_bins(sr, hop)[1]]
     if f0 and f0_estimator != "dio":
         summary["f0_estimator"] = f0_estimator
     summary["skipped"] = len(skipped)

@@ -680,6 +680,26 @@ int fs2_dtw_prosody(const int32_t* pi, const int32_t* pj, long ldq, const int32_
 int fs2_prosody_voiced(const double* f0, long ldf, const int32_t* lens, double* out, long ldo, int32_t* nv, double* stats, long lds,
                        int B, int Tmax, fs2_stream_t stream);
 
+/* ---- over-smoothing: global variance and modulation spectrum (csrc/fs2_modspec.hip; specification: fastspeech2_amd/modspec.py) ----
+ * Trajectories c [B][Tmax][K] f64 with batch / frame strides in elements (ldc_t >= K, ldc_b >= Tmax ldc_t) and unit stride in k; row
+ * b has lens[b] frames (int32, device), 1 <= Tmax <= fs2_dtw_max_frames(), 1 <= K <= 128.  Nothing at a frame >= lens[b] is read; a
+ * row with lens[b] < 1 is left alone.  fp64, no atomics; every sum runs in ascending order in one thread with its rounding errors
+ * carried in a second word: the same input gives the same bytes.
+ * fs2_modspec_nfft: the transform length N = 4096, twice the frame bound. */
+int fs2_modspec_nfft(void);
+/* mom[b][k][0..2) = {mean = (sum_t c) / T, M2 = sum_t (c - mean)^2 in a second pass}; strides ldm_k >= 2, ldm_b >= K ldm_k */
+int fs2_traj_moments(const double* c, long ldc_b, long ldc_t, const int32_t* lens, double* mom, long ldm_b, long ldm_k, int B, int Tmax,
+                     int K, fs2_stream_t stream);
+/* With x[t] = c[b][t][k] - mean[b][k] (mean: any strides ldm_b, ldm_k, so the mom of fs2_traj_moments serves), X[f] = sum_t x[t]
+ * (cos - i sin)(2 pi ((f t) mod N) / N) against twiddle [N][2] = {cos, sin}(2 pi j / N), the caller's device table (no sine is
+ * evaluated here), and ms[f] = ln(|X[f]|^2 / T + floor), f = 0 .. N / 2: bands[b][k][j] = (10 / ln 10) times the mean of ms over the
+ * bins [bins[2 j], bins[2 j + 1]), j < n_bands (strides ldo_k >= n_bands, ldo_b >= K ldo_k), and, when logms is not NULL,
+ * logms[b][k][f] = ms[f] (strides ldl_k >= N / 2 + 1, ldl_b >= K ldl_k).  bins: HOST memory, 1 <= n_bands <= 16 non-empty, ascending,
+ * disjoint ranges within [0, N / 2 + 1); floor > 0; B <= 65535.  Nothing beyond those counts is written. */
+int fs2_modspec(const double* c, long ldc_b, long ldc_t, const int32_t* lens, const double* mean, long ldm_b, long ldm_k,
+                const double* twiddle, const int32_t* bins, int n_bands, double floor_, double* bands, long ldo_b, long ldo_k,
+                double* logms, long ldl_b, long ldl_k, int B, int Tmax, int K, fs2_stream_t stream);
+
 /* ---- time-aligned intelligibility: STOI and ESTOI (csrc/fs2_stoi.hip; specification: fastspeech2_amd/stoi.py) ----
  * Ragged batches of time-aligned pairs at 10 kHz: float32 rows x (clean) and y (B, ldx) sharing one device lens, fp64 after the load,
  * no atomics, fixed-order sums: the same input gives the same bytes.  Nothing at or beyond lens[b] is read.  Frames of 256 samples at

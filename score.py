@@ -3,7 +3,7 @@
 
     python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
                     [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--f0 {dio,pyin}] [--aligned] [--max_len_diff N]
-                    [--out scores.jsonl]
+                    [--smoothing] [--out scores.jsonl]
 
 For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
 is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
@@ -23,7 +23,11 @@ StoneMask, an independent estimator to cross-check the pitch scores with; rows a
 With `--aligned` the synthesized wavs are taken to share the recording's time axis, as copysynth.py's do (a recorded mel through the
 vocoder): a pair whose lengths differ by more than `--max_len_diff` samples (default 2 hop_length) is skipped as not time-aligned,
 every other pair is cut to its shorter side and also gets STOI and ESTOI (fastspeech2_amd/stoi.py: the published algorithms on this
-project's own resampler; agreement with pystoi or the authors' MATLAB code is unmeasured), and the summary their corpus means."""
+project's own resampler; agreement with pystoi or the authors' MATLAB code is unmeasured), and the summary their corpus means.
+With `--smoothing` every row and the summary also carry the two published measures of over-smoothed spectra, taken of both sides'
+cepstra (fastspeech2_amd/modspec.py): the global variance per coefficient and its ratio in dB, and the modulation spectrum in bands
+from 0 to the frame-rate Nyquist with the distance between the two sides.  A ratio or a band difference below 0 says the synthesized
+trajectories vary too little; the numbers compare runs of this tool, and a value near 0 is not a claim of naturalness."""
 import argparse
 import json
 import sys
@@ -55,6 +59,9 @@ def parse_args(argv=None):
                         help="the wavs are sample-aligned with the recordings (copysynth.py): also STOI and ESTOI per pair")
     parser.add_argument("--max_len_diff", type=int, default=None,
                         help="--aligned: skip a pair whose lengths differ by more samples than this (default 2 hop_length)")
+    parser.add_argument("--smoothing", action="store_true",
+                        help="also the global variance and the modulation spectrum of both sides' cepstra: how over-smoothed the "
+                             "synthesized spectra are")
     parser.add_argument("--out", type=str, default="scores.jsonl")
     parser.add_argument("--device", type=str, default="cuda")
     return parser.parse_args(argv)
@@ -69,7 +76,7 @@ def main(argv=None, score_fn=None, aligned_fn=None):
                                              ref_dir=args.ref_dir, trim=not args.no_trim, f0=not args.no_f0, n_mcep=args.n_mcep,
                                              score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha,
                                              prosody=args.prosody, f0_estimator=args.f0, aligned=args.aligned,
-                                             max_len_diff=args.max_len_diff, aligned_fn=aligned_fn)
+                                             max_len_diff=args.max_len_diff, aligned_fn=aligned_fn, smoothing=args.smoothing)
     except ValueError as e:
         sys.exit(str(e))
     for name, reason in skipped:
