@@ -226,8 +226,13 @@ class SynthPipeline:
 
     for batch, output, wavs in SynthPipeline(model, vocoder, configs)(batches): ...   # in batch order, `voc_streams` batches behind"""
 
-    def __init__(self, model, vocoder, configs, control_values=(1.0, 1.0, 1.0), device=None, path=None, write=False, voc_streams=3):
+    def __init__(self, model, vocoder, configs, control_values=(1.0, 1.0, 1.0), device=None, path=None, write=False, voc_streams=3,
+                 postfilter=None):
         self.model, self.vocoder = model, vocoder
+        # (tables, k) of fastspeech2_amd.postfilter: the post-net mel is filtered on the acoustic stream before the vocoder reads it
+        # and is what the pipeline yields in position 1; None: no launch, sample or byte differs from the pipeline without it
+        self.postfilter = postfilter
+        self.passed_through = 0                 # rows the postfilter copied unchanged (too short or too long for it)
         self.preprocess_config, self.model_config = configs[0], configs[1]
         assert self.model_config["vocoder"]["model"] in ("HiFi-GAN", "MelGAN")
         self.controls = control_values
@@ -257,6 +262,8 @@ class SynthPipeline:
         with torch.no_grad():
             with torch.cuda.stream(self.s_ac):
                 out = self.model(*(batch[2:]), p_control=p, e_control=e, d_control=d)
+                if self.postfilter is not None:
+                    out = self._postfiltered(out)
                 lengths = _sample_lengths(out[9], self.preprocess_config)
                 ready = torch.cuda.Event()
                 ready.record(self.s_ac)
@@ -276,6 +283,18 @@ class SynthPipeline:
                 done.record(s_voc)
         # `out` and `pcm` were allocated on one stream and are read on another: they stay referenced until `done` has been waited for
         return batch, out, pcm, host, lengths, done
+
+    def _postfiltered(self, out):
+        """the model's output with its post-net mel (position 1) through the modulation-spectrum postfilter, on the current stream,
+        with the host lengths the engine left on out[9]"""
+        from . import postfilter as Postfilter
+        tables, k = self.postfilter
+        host = getattr(out[9], "_fs2_host", None)
+        lens = [int(n) for n in (host if host is not None else out[9].tolist())]
+        mel = Postfilter.apply(out[1], lens, tables, k)
+        if mel is not out[1]:
+            self.passed_through += Postfilter.pass_through(lens)
+        return type(out)(out[:1]) + type(out)((mel,)) + type(out)(out[2:])
 
     def _finish(self, item):
         batch, out, pcm, host, lengths, done = item

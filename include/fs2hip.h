@@ -700,6 +700,26 @@ int fs2_modspec(const double* c, long ldc_b, long ldc_t, const int32_t* lens, co
                 const double* twiddle, const int32_t* bins, int n_bands, double floor_, double* bands, long ldo_b, long ldo_k,
                 double* logms, long ldl_b, long ldl_k, int B, int Tmax, int K, fs2_stream_t stream);
 
+/* ---- modulation-spectrum postfilter (csrc/fs2_msfilter.hip; specification: fastspeech2_amd/postfilter.py) ----
+ * fs2_ms_stats_update: folds the rows b = 0 .. B - 1 of logms [B][K][N / 2 + 1] (what fs2_modspec writes; strides ldl_k >= N / 2 + 1,
+ * ldl_b >= K ldl_k) whose keep[b] (int32, device) is not 0 into state[k][f][0..2) = {mean, M2} (stride lds_k >= 2 (N / 2 + 1)), in
+ * ascending b with Welford's update; n_before is the number of rows folded into state so far (0: state is not read).  One thread per
+ * (k, f), no atomics: the same input gives the same bytes. */
+int fs2_ms_stats_update(const double* logms, long ldl_b, long ldl_k, const int32_t* keep, double* state, long lds_k, long n_before,
+                        int B, int K, fs2_stream_t stream);
+/* The postfilter on trajectories c [B][Tmax][K], float32 (is_f64 = 0) or float64 (is_f64 = 1), strides in elements as fs2_modspec
+ * takes them, into y of the same type (ldy_t >= K, ldy_b >= Tmax ldy_t; y must not overlap c).  With x = c - mean, X and ms[f] as
+ * fs2_modspec defines them and the rows k of the tables mu_n, sd_n, mu_g, sd_g [K][N / 2 + 1] f64 (stride lds_k >= N / 2 + 1):
+ * r = sd_n / sd_g (1 where sd_g is not above 0), ln g[f] = 0.5 k_emph (r (ms - mu_g) + mu_n - ms) clamped to +- max_gain_db
+ * (ln 10) / 20, g[0] = 1, y[t] = mean + (1 / N)(X[0] + 2 sum_{0 < f < N / 2} Re(g X e^{+2 pi i f t / N}) + g X[N / 2] (-1)^t), t < lens[b].
+ * fp64 arithmetic whatever the type.  A row with lens[b] < min_frames is copied to y; a row with lens[b] < 1 is left alone; nothing
+ * at a frame >= lens[b] or a coefficient >= K is read or written.  0 <= k_emph <= 1, floor > 0, 0 <= max_gain_db <= 200,
+ * min_frames >= 1, 1 <= Tmax <= fs2_dtw_max_frames(), 1 <= K <= 128, B <= 65535. */
+int fs2_ms_filter(const void* c, long ldc_b, long ldc_t, const int32_t* lens, const double* mean, long ldm_b, long ldm_k,
+                  const double* twiddle, const double* mu_n, const double* sd_n, const double* mu_g, const double* sd_g, long lds_k,
+                  double k_emph, double floor_, double max_gain_db, int min_frames, void* y, long ldy_b, long ldy_t, int is_f64, int B,
+                  int Tmax, int K, fs2_stream_t stream);
+
 /* ---- time-aligned intelligibility: STOI and ESTOI (csrc/fs2_stoi.hip; specification: fastspeech2_amd/stoi.py) ----
  * Ragged batches of time-aligned pairs at 10 kHz: float32 rows x (clean) and y (B, ldx) sharing one device lens, fp64 after the load,
  * no atomics, fixed-order sums: the same input gives the same bytes.  Nothing at or beyond lens[b] is read.  Frames of 256 samples at

@@ -6,6 +6,8 @@
 
 The acoustic model and the HiFi-GAN generator run as HIP kernels; wavs land in train_config.path.result_path.
 With --griffin_iters N the wavs come from N Griffin-Lim iterations on the post-net mel instead (no vocoder checkpoint needed).
+With --postfilter STATS.npz (written by `python postfilter.py train`) the post-net mel goes through the modulation-spectrum
+postfilter (fastspeech2_amd/postfilter.py) before the vocoder or Griffin-Lim reads it; --postfilter_k is its emphasis coefficient.
 Batch mode reads phoneme strings (the `{...}` field of train.txt / val.txt), exactly what the reference's TextDataset
 does.  Single mode takes the phoneme string directly: the grapheme-to-phoneme step of the reference (g2p_en / pypinyin +
 lexicon, synthesize.py:20-84) is host-side string processing outside the hot path and its packages are not in this
@@ -27,20 +29,22 @@ from fastspeech2_amd.text import text_to_sequence
 from fastspeech2_amd.utils import SynthPipeline, get_model, get_vocoder
 
 
-def synthesize(model, step, configs, vocoder, batchs, control_values, device=None):
+def synthesize(model, step, configs, vocoder, batchs, control_values, device=None, postfilter=None):
     preprocess_config, model_config, train_config = configs
     pitch_control, energy_control, duration_control = control_values
     device = device or torch.device("cuda", torch.cuda.current_device())
     n = 0
     # the reference's loop (synthesize.py:87-103) as a stream pipeline: the next batch's acoustic model under the previous batches' vocoders
     pipeline = SynthPipeline(model, vocoder, configs, control_values, device=device, path=train_config["path"]["result_path"],
-                             write=True)
+                             write=True, postfilter=postfilter)
     for batch, _output, _wavs in pipeline(DevicePrefetcher(batchs, device)):
         n += len(batch[0])
+    if postfilter is not None and pipeline.passed_through:
+        print(f"postfilter: {pipeline.passed_through} utterances too short or too long for it went through unchanged")
     return n
 
 
-def synthesize_griffin_lim(model, configs, batchs, control_values, n_iters, device=None):
+def synthesize_griffin_lim(model, configs, batchs, control_values, n_iters, device=None, postfilter=None):
     """--griffin_iters N: the post-net mel of each utterance (cut at its mel_len) -> Griffin-Lim (N iterations, audio/tools.py:18-34
     inv_mel_spec on the GPU, one ragged launch sequence per batch) -> float32 wavs; no vocoder is loaded."""
     from fastspeech2_amd.audio import TacotronSTFT, mels_to_wavs_griffin_lim
@@ -55,7 +59,12 @@ def synthesize_griffin_lim(model, configs, batchs, control_values, n_iters, devi
     for batch in DevicePrefetcher(batchs, device):
         with torch.no_grad():
             out = model(*(batch[2:]), p_control=pitch_control, e_control=energy_control, d_control=duration_control)
-            wavs = mels_to_wavs_griffin_lim(out[1].transpose(1, 2), out[9], stft, n_iters)
+            mel = out[1]
+            if postfilter is not None:
+                from fastspeech2_amd import postfilter as Postfilter
+                host = getattr(out[9], "_fs2_host", None)
+                mel = Postfilter.apply(mel, host if host is not None else out[9].tolist(), postfilter[0], postfilter[1])
+            wavs = mels_to_wavs_griffin_lim(mel.transpose(1, 2), out[9], stft, n_iters)
         _write_wavs(train_config["path"]["result_path"], batch[0], wavs, preprocess_config)
         n += len(batch[0])
     return n
@@ -123,7 +132,14 @@ def parse_args(argv=None):
                         help="a model trained by `python g2p.py train`: --mode single takes free English text (without it, a phoneme string in braces)")
     parser.add_argument("--griffin_iters", type=int, default=0,
                         help="N > 0: waveforms by N Griffin-Lim iterations on the post-net mel (float32 wavs, no vocoder loaded); 0 = HiFi-GAN")
-    return parser.parse_args(argv)
+    parser.add_argument("--postfilter", default=None, metavar="STATS.npz",
+                        help="statistics written by `python postfilter.py train`: the post-net mel goes through the modulation-spectrum "
+                             "postfilter before the vocoder (or Griffin-Lim) reads it")
+    parser.add_argument("--postfilter_k", type=float, default=0.85, help="the postfilter's emphasis coefficient in [0, 1]; 0 = no filter")
+    args = parser.parse_args(argv)
+    if not 0.0 <= args.postfilter_k <= 1.0:
+        parser.error("--postfilter_k must lie in [0, 1]")
+    return args
 
 
 def main(args):
@@ -148,10 +164,14 @@ def main(args):
     else:
         batchs = single_batch(args, preprocess_config)
     controls = (args.pitch_control, args.energy_control, args.duration_control)
+    postfilter = None
+    if args.postfilter is not None:
+        from fastspeech2_amd import postfilter as Postfilter
+        postfilter = (Postfilter.load(args.postfilter, preprocess_config), args.postfilter_k)
     if args.griffin_iters > 0:
-        n = synthesize_griffin_lim(model, configs, batchs, controls, args.griffin_iters, device=device)
+        n = synthesize_griffin_lim(model, configs, batchs, controls, args.griffin_iters, device=device, postfilter=postfilter)
     else:
-        n = synthesize(model, args.restore_step, configs, vocoder, batchs, controls, device=device)
+        n = synthesize(model, args.restore_step, configs, vocoder, batchs, controls, device=device, postfilter=postfilter)
     print(f"[rank {rank}] synthesized {n} utterances -> {train_config['path']['result_path']}")
 
 
