@@ -76,6 +76,14 @@ gv_ratio_db, ms_db_ref, ms_db_syn, ms_band_db_ref, ms_band_db_syn and ms_dist_db
 ms_dist_db_corpus, gv_ratio_db_by_coef, the means gv_ratio_db_mean and ms_dist_db_mean with their `_nan_utterances` counts, and
 smoothing_too_short_utterances.  Without `smoothing` every launch, every row and the summary are what they are without this paragraph.
 
+Wavelet prosody (`wavelet=True`, `score.py --wavelet`; needs F0, not `prosody`).  The continuous wavelet transform of both sides'
+interpolated, normalised ln F0 at ten scales one octave apart, compared along the cepstral path, specified in full in the docstring
+of `cwt`: every row also carries cwt_corr, cwt_rmse, cwt_level_corr, cwt_level_rmse, cwt_power_db_ref, cwt_power_db_syn,
+cwt_power_ratio_db, lf0_mean_ref, lf0_mean_syn, lf0_std_ref and lf0_std_syn, the summary cwt_scales_ms, the `_mean`, `_weighted` and
+`_nan_utterances` lists of the first four, cwt_power_ratio_db_by_scale and wavelet_flat_utterances.  It scores the same F0 track as
+the other F0 numbers (`f0_estimator`).  Without `wavelet` every launch, every row and the summary are what they are without this
+paragraph.
+
 Storage.  The local costs and backpointers of a pair are held skewed, cell (i, j) at row (i + j) mod T2, column i of a (T2max, T1max)
 matrix: an anti-diagonal is contiguous, the buffer is no larger than the plain one (`unskew` undoes it for a test).  The accumulated
 costs never leave the chip.  Determinism: no atomics, sums in a fixed order; two runs give byte-identical scores.
@@ -96,6 +104,7 @@ PROSODY_SUMS = 8                                            # gross, n, V/UV mis
 PROSODY_FRAME_BYTES = 24                                    # per frame: the compacted contour (8 B) and its share of the second path
 CORR_FLOOR = 1e-24
 SMOOTHING_BANDS = 8                                         # at most: the bands of `modspec.EDGES_HZ`
+WAVELET_FRAME_BYTES = 88                                    # per frame and side: z and the ten scales of its transform, float64
 PROSODY_SCORES = ("gpe", "ffe", "f0_corr", "f0_dtw_hz", "energy_mae", "energy_mae_rel")
 
 
@@ -453,17 +462,21 @@ def summarize(rows):
     if "gv_ratio_db" in rows[0]:
         from . import modspec as Modspec
         out.update(Modspec.summarize(rows))
+    if "cwt_corr" in rows[0]:
+        from . import cwt as Cwt
+        out.update(Cwt.summarize(rows))
     return out
 
 
-def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0, prosody=False, smoothing=False):
+def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0, prosody=False, smoothing=False, wavelet=False):
     """What a batch of n pairs padded to (T1, T2) frames holds on the device: 9 B per (i, j) cell (local cost + backpointer), the
     audio, its STFT workspace and mel (about 40 B per sample), cepstra, F0 and the path; with `fft_size` (cepstra="world") also the
     spectral envelope, fft_size / 2 + 1 float64 bins per frame and side; with `prosody` the compacted contours and the second path
     (24 B per frame; the contour DTW's cells reuse the first DTW's, released by then); with `smoothing` the moments and band values
-    of both sides, (2 + SMOOTHING_BANDS) float64 per coefficient and side."""
+    of both sides, (2 + SMOOTHING_BANDS) float64 per coefficient and side; with `wavelet` the normalised contour and the ten scales
+    of its transform, 88 B per frame and side."""
     return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64 + (fft_size // 2 + 1) * 8 * (fft_size > 0)
-                                                    + PROSODY_FRAME_BYTES * bool(prosody))
+                                                    + PROSODY_FRAME_BYTES * bool(prosody) + WAVELET_FRAME_BYTES * bool(wavelet))
                 + 2 * n_mcep * (2 + SMOOTHING_BANDS) * 8 * bool(smoothing))
 
 
@@ -485,7 +498,7 @@ def frame_counts(n_samples, sampling_rate, hop_length, f0=True):
 
 
 def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None, f0=True, device="cuda", budget=4 << 30,
-                cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", smoothing=False):
+                cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", smoothing=False, wavelet=False):
     """Scores of (recorded, synthesized) pairs of float32 waveforms at `sampling_rate` -> one dict per pair (module docstring), in
     the order given.  `stft` is the config's `audio.TacotronSTFT`.  Pairs are packed longest first into ragged batches under `budget`
     bytes of device buffers; per batch: both sides through one pinned staging buffer, mel -> cepstra -> local cost -> scan ->
@@ -501,13 +514,19 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
     its own DIO + StoneMask track whatever the estimator.  The pYIN workspace of a batch (`pyin.workspace_bytes`) counts towards
     `budget`.  With `smoothing` the two kernels of `modspec` run on both sides' cepstra, whichever they are, before these are
     released, their results ride in the batch's one D2H copy, and every row also carries the over-smoothing keys of the module
-    docstring."""
+    docstring.  With `wavelet` (needs `f0`) the three kernels of `cwt` run on both sides' scored F0 track, the path stays alive until
+    the path sums are taken, the results ride in the same D2H copy, and every row also carries the wavelet keys."""
+    from . import cwt as Cwt
     from . import envelope as Env
     from . import modspec as Modspec
     if f0_estimator not in ("dio", "pyin"):
         raise ValueError(f"f0_estimator must be 'dio' or 'pyin', got {f0_estimator!r}")
     if prosody and not f0:
         raise ValueError("prosody scores need F0: prosody=True cannot go with f0=False")
+    if wavelet and not f0:
+        raise ValueError("wavelet prosody scores need F0: wavelet=True cannot go with f0=False")
+    if wavelet:
+        Cwt.scales(sampling_rate, hop_length)                               # a hop above 20 ms is refused before any work
     if prosody and stft is None:
         raise ValueError("prosody scores need the STFT for the frame energy: stft=None cannot go with prosody=True")
     if cepstra not in ("mel", "world"):
@@ -560,7 +579,7 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
             return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), scored if f0 else None, energy
         return cepstra_fn(mel, frames, n_mcep), scored, energy
 
-    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody, smoothing)     # noqa: E731
+    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody, smoothing, wavelet)     # noqa: E731
     if f0 and f0_estimator == "pyin":                                       # one side's pYIN chunk workspace lives at a time
         from . import pyin as Pyin
         cepstral = cost
@@ -575,6 +594,11 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
         cols = [total, plen.to(torch.float64)]
         if f0:
             cols += list(f0_on_path(pi, pj, plen, f0a, al, f0b, bl).unbind(1))
+        if wavelet:                                                         # before the path is released below
+            Wa, pwa, sta = Cwt.measure(f0a, al, sampling_rate, hop_length)
+            Wb, pwb, stb = Cwt.measure(f0b, bl, sampling_rate, hop_length)
+            smooth += [Cwt.on_path(pi, pj, plen, Wa, al, Wb, bl).reshape(len(batch), -1), pwa, sta, pwb, stb]
+            del Wa, Wb
         if prosody:
             cols += list(prosody_on_path(pi, pj, plen, f0a, al, f0b, bl, ea, eb).unbind(1))
             del pi, pj
@@ -582,17 +606,20 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
             w, nw, sw = voiced_contours(f0b, bl)
             ctotal, cplen, _, _, _ = contour_dtw(u, nu.cpu(), w, nw.cpu())    # the voiced counts: one small D2H copy per side
             cols += list(su.unbind(1)) + list(sw.unbind(1)) + [ctotal, cplen.to(torch.float64)]
-        n_cols = len(cols)
+        n_cols, n_smooth = len(cols), 2 * n_mcep * (1 + len(bins)) if smoothing else 0
         scores = torch.stack(cols, dim=1)
-        host = (torch.cat([scores] + smooth, dim=1) if smoothing else scores).cpu().numpy()     # the batch's one D2H copy of the scores
+        host = (torch.cat([scores] + smooth, dim=1) if smooth else scores).cpu().numpy()     # the batch's one D2H copy of the scores
         for r, i in enumerate(batch):
             rows[i] = scores_from_sums(host[r, 0], host[r, 1], al[r], bl[r], host[r, 2:5] if f0 else None)
             if prosody:
                 q = host[r, 5:n_cols]
                 rows[i].update(prosody_scores(q[:8], host[r, 1], q[8:13], q[13:18], q[18], q[19]))
             if smoothing:
-                m2a, ba, m2b, bb = np.split(host[r, n_cols:], np.cumsum([n_mcep, n_mcep * len(bins), n_mcep])[:3])
+                m2a, ba, m2b, bb = np.split(host[r, n_cols:n_cols + n_smooth], np.cumsum([n_mcep, n_mcep * len(bins), n_mcep])[:3])
                 rows[i].update(Modspec.row_scores(m2a, ba.reshape(n_mcep, -1), al[r], m2b, bb.reshape(n_mcep, -1), bl[r]))
+            if wavelet:
+                ws, pwa, sta, pwb, stb = np.split(host[r, n_cols + n_smooth:], np.cumsum([Cwt.COMPONENTS * 4, Cwt.SCALES, 4, Cwt.SCALES]))
+                rows[i].update(Cwt.row_scores(ws, host[r, 1], pwa, al[r], sta, pwb, bl[r], stb))
             if world:
                 rows[i].update(cepstra="world", alpha=alpha, fft_size=fft_size)
             if f0 and f0_estimator != "dio":
@@ -656,7 +683,7 @@ class _Rates:
 
 def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=None, score_fn=None,
         device="cuda", cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", aligned=False, max_len_diff=None, aligned_fn=None,
-        smoothing=False):
+        smoothing=False, wavelet=False):
     """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
     replaces the device stage (called with `prosody=True` as a keyword when that is asked for).  Returns (rows, skipped, summary).
     With cepstra="world" the rows and the summary also say cepstra, alpha and fft_size; with "mel" they are what they were before
@@ -669,7 +696,9 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
     and the number of those that are.  `aligned_fn(ref_wavs, syn_wavs) -> [dict]` replaces that device stage.  Without `aligned`
     every row, every summary key and every launch is what it is without this paragraph.  `smoothing` (score.py --smoothing) adds
     the over-smoothing keys of `modspec` to every row and to the summary, with ms_bands_hz, the band edges in Hz at this config's
-    frame rate; a `score_fn` is then called with `smoothing=True` as a keyword."""
+    frame rate; a `score_fn` is then called with `smoothing=True` as a keyword.  `wavelet` (score.py --wavelet) adds the wavelet
+    prosody keys of `cwt` to every row and to the summary, is refused with f0=False before a file is read, and reaches a `score_fn`
+    as `wavelet=True`."""
     import json
     pp = config["preprocessing"]
     sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
@@ -677,6 +706,11 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
         raise ValueError("--prosody needs F0 and cannot go with --no_f0")
     if f0_estimator not in ("dio", "pyin"):
         raise ValueError(f"f0_estimator must be 'dio' or 'pyin', got {f0_estimator!r}")
+    if wavelet and not f0:
+        raise ValueError("--wavelet needs F0 and cannot go with --no_f0")
+    if wavelet:
+        from . import cwt as Cwt
+        Cwt.scales(sr, hop)                                                 # refused before a file is read
     world_keys = {}
     if cepstra == "world":                                                  # refused before a file is read
         from . import envelope as Env
@@ -704,9 +738,10 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
         stft = Audio.TacotronSTFT(pp["stft"]["filter_length"], hop, pp["stft"]["win_length"], pp["mel"]["n_mel_channels"], sr,
                                   pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
         score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device, cepstra=cepstra,     # noqa: E731
-                                            alpha=alpha, prosody=prosody, f0_estimator=f0_estimator, smoothing=smoothing)
-    elif prosody or smoothing:
-        given, asked = score_fn, {k: True for k, v in (("prosody", prosody), ("smoothing", smoothing)) if v}
+                                            alpha=alpha, prosody=prosody, f0_estimator=f0_estimator, smoothing=smoothing,
+                                            wavelet=wavelet)
+    elif prosody or smoothing or wavelet:
+        given, asked = score_fn, {k: True for k, v in (("prosody", prosody), ("smoothing", smoothing), ("wavelet", wavelet)) if v}
         score_fn = lambda r, s: given(r, s, **asked)                         # noqa: E731
     scores = score_fn([it["ref"] for it in items], [it["syn"] for it in items]) if items else []
     rows = [{"basename": it["basename"], "speaker": it["speaker"], "reference_window": it["window"], **sc}

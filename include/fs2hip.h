@@ -720,6 +720,32 @@ int fs2_ms_filter(const void* c, long ldc_b, long ldc_t, const int32_t* lens, co
                   double k_emph, double floor_, double max_gain_db, int min_frames, void* y, long ldy_b, long ldy_t, int is_f64, int B,
                   int Tmax, int K, fs2_stream_t stream);
 
+/* ---- wavelet prosody scores (csrc/fs2_cwt.hip; specification: fastspeech2_amd/cwt.py) ----
+ * Ragged batches of f64 rows; row b has lens[b] frames (int32, device), 1 <= Tmax <= fs2_dtw_max_frames().  Nothing at a frame >=
+ * lens[b] is read or written; a row with lens[b] < 1 is left alone.  No atomics; every sum carries its rounding errors in a second
+ * word, per lane in ascending order and then by a fixed tree: the same input gives the same bytes, whatever rows are beside it.
+ * fs2_cwt_scales: the number of scales, 10. */
+int fs2_cwt_scales(void);
+/* The normalised continuous ln F0 of the tracks f0 [B][ldf] in Hz (a frame is voiced where f0 > 0): x = ln f0 at a voiced frame,
+ * x[t0] + (x[t1] - x[t0]) * ((t - t0) / (t1 - t0)) between the nearest voiced frames t0 < t < t1, the first / last voiced value
+ * before / after them; m = (sum x) / T, sd = sqrt(sum (x - m)^2 / T) in a second pass, z[b][t] = (x[t] - m) / sd, and
+ * stats[b][0..4) = {voiced frames, m, sd, flat}; flat = 1 without a voiced frame (then m = sd = 0) or with sd <= 1e-12, and z is
+ * then 0 over [0, T).  Strides ldf, ldz >= Tmax, lds >= 4; z must not be f0. */
+int fs2_cwt_contour(const double* f0, long ldf, const int32_t* lens, double* z, long ldz, double* stats, long lds, int B, int Tmax,
+                    fs2_stream_t stream);
+/* w[b][i][t] = sum over u in [0, lens[b]), ascending, of z[b][u] tab[i][|u - t|], i < 10, with tab [10][ldt] the caller's device
+ * tables, of which support[i] entries count (HOST memory; 1 <= support[i] <= min(ldt, 2048)) and the rest is taken as 0, and
+ * power[b][i] = sum_t w[b][i][t]^2.  Strides ldz, ldw_i >= Tmax, ldw_b >= 10 ldw_i, ldp >= 10; B <= 65535. */
+int fs2_cwt_transform(const double* z, long ldz, const int32_t* lens, const double* tab, long ldt, const int32_t* support, double* w,
+                      long ldw_b, long ldw_i, double* power, long ldp, int B, int Tmax, fs2_stream_t stream);
+/* Along the path (pi, pj, plen as fs2_dtw_backtrack writes them), for the 15 components c of w_ref / w_syn (as fs2_cwt_transform
+ * writes them): c < 10 the scale c, c = 10 + j the level w[2 j] + w[2 j + 1], with x = the component of w_ref at pi[k] and y that of
+ * w_syn at pj[k]: sums[p][c][0..4) = {Sxx, Syy, Sxy about the two means of a first pass, Sd2 = sum (x - y)^2}; all 0 for a pair
+ * without a path cell.  Strides ldr_i >= T1max, ldr_b >= 10 ldr_i (w_syn alike), ldo_c >= 4, ldo_b >= 15 ldo_c; B <= 65535. */
+int fs2_cwt_on_path(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* plen, const double* w_ref, long ldr_b, long ldr_i,
+                    const double* w_syn, long lds_b, long lds_i, const int32_t* alens, const int32_t* blens, double* sums, long ldo_b,
+                    long ldo_c, int B, int T1max, int T2max, fs2_stream_t stream);
+
 /* ---- time-aligned intelligibility: STOI and ESTOI (csrc/fs2_stoi.hip; specification: fastspeech2_amd/stoi.py) ----
  * Ragged batches of time-aligned pairs at 10 kHz: float32 rows x (clean) and y (B, ldx) sharing one device lens, fp64 after the load,
  * no atomics, fixed-order sums: the same input gives the same bytes.  Nothing at or beyond lens[b] is read.  Frames of 256 samples at

@@ -3,7 +3,7 @@
 
     python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
                     [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--f0 {dio,pyin}] [--aligned] [--max_len_diff N]
-                    [--smoothing] [--out scores.jsonl]
+                    [--smoothing] [--wavelet] [--out scores.jsonl]
 
 For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
 is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
@@ -27,7 +27,13 @@ project's own resampler; agreement with pystoi or the authors' MATLAB code is un
 With `--smoothing` every row and the summary also carry the two published measures of over-smoothed spectra, taken of both sides'
 cepstra (fastspeech2_amd/modspec.py): the global variance per coefficient and its ratio in dB, and the modulation spectrum in bands
 from 0 to the frame-rate Nyquist with the distance between the two sides.  A ratio or a band difference below 0 says the synthesized
-trajectories vary too little; the numbers compare runs of this tool, and a value near 0 is not a claim of naturalness."""
+trajectories vary too little; the numbers compare runs of this tool, and a value near 0 is not a claim of naturalness.
+With `--wavelet` (not with `--no_f0`; it goes with either `--f0` and either `--cepstra`, and does not need `--prosody`) every row and
+the summary also say at which time scale the pitch contour departs from the recording (fastspeech2_amd/cwt.py): both sides' F0 is
+interpolated over the unvoiced frames, taken as ln F0 and normalised per utterance, transformed by a Mexican-hat wavelet at ten
+scales from 20 ms to 10.24 s, and the two transforms are correlated along the DTW path, per scale and per level of two adjacent
+scales, with the power per scale of each side and the mean and deviation of ln F0.  The constants are FastSpeech 2's pitch
+spectrogram's as remembered, not checked against the papers; the numbers compare runs of this tool."""
 import argparse
 import json
 import sys
@@ -62,6 +68,9 @@ def parse_args(argv=None):
     parser.add_argument("--smoothing", action="store_true",
                         help="also the global variance and the modulation spectrum of both sides' cepstra: how over-smoothed the "
                              "synthesized spectra are")
+    parser.add_argument("--wavelet", action="store_true",
+                        help="also the wavelet prosody scores: correlation, RMSE and power of the continuous ln F0 at ten time scales "
+                             "(needs F0)")
     parser.add_argument("--out", type=str, default="scores.jsonl")
     parser.add_argument("--device", type=str, default="cuda")
     return parser.parse_args(argv)
@@ -76,7 +85,8 @@ def main(argv=None, score_fn=None, aligned_fn=None):
                                              ref_dir=args.ref_dir, trim=not args.no_trim, f0=not args.no_f0, n_mcep=args.n_mcep,
                                              score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha,
                                              prosody=args.prosody, f0_estimator=args.f0, aligned=args.aligned,
-                                             max_len_diff=args.max_len_diff, aligned_fn=aligned_fn, smoothing=args.smoothing)
+                                             max_len_diff=args.max_len_diff, aligned_fn=aligned_fn, smoothing=args.smoothing,
+                                             wavelet=args.wavelet)
     except ValueError as e:
         sys.exit(str(e))
     for name, reason in skipped:
