@@ -1,0 +1,309 @@
+// fs2_hnr.hip — the harmonics-to-noise ratio of Boersma (1993) per frame, from the window-corrected autocorrelation searched around
+// a given F0 track, its moments per side and its comparison along a DTW path.  fp64 after the float32 audio is loaded, ragged
+// batches of rows of at most 2048 frames.  The specification is the docstring of fastspeech2_amd/hnr.py; tests/hnr_ref.py restates
+// it in numpy (explicit loops, np.correlate for the lag sums).
+//
+// Every sum here carries its rounding errors in a second word (the two-sum of Knuth for the additions, an fma for the error of
+// each product), per lane in ascending order and then by a fixed tree or in a fixed ascending order: the result is the sum of the
+// exactly evaluated terms rounded once, except in cases too rare to meet.  No atomics; nothing at a frame >= frames[b] is read or
+// written and no sample >= lens[b] is read; the same input gives the same bytes, and a row's bytes do not depend on the rows beside
+// it (a workgroup sees one frame, one row or one pair only).
+//
+//   fs2_hnr_frames   one workgroup per frame, the frame in LDS (N = 2 h + 1 doubles, dynamic: up to 64 KiB of the CU's 160).  The
+//                    mean, then a[k] = (x[k] - mean) w[k] in place and r0 = sum a^2.  A lane owns one lag tau and a wave one quarter
+//                    of the k range: a[k] is a broadcast and a[k + tau] unit-stride across the lanes, both conflict-free.  The four
+//                    quarters of a lag are added in ascending order by its lane.  Lags go 64 at a time.  Lane 0 then takes the
+//                    first maximum, the parabola and the logarithm.  About 10 fp64 operations per term, bound by arithmetic.
+//   fs2_hnr_side     one workgroup per row: the number, the mean and, in a second pass, the central M2 of hnr over the valid frames.
+//   fs2_hnr_on_path  one workgroup per pair: over the path cells whose two frames are both valid the count and the two means in
+//                    a first pass, Sxx, Syy, Sxy about them and Sd2 in a second.
+#include "fs2_common.h"
+
+#define HN_MAX_FRAMES 2048          // = fs2_dtw_max_frames()
+#define HN_MAX_WINDOW 8191
+#define HN_MAX_LDS (160 * 1024)
+#define HN_NT 256
+#define HN_WAVE 64
+#define HN_WAVES (HN_NT / HN_WAVE)
+#define HN_SEARCH 1.2
+#define HN_R_LO 1e-3
+#define HN_R_HI (1.0 - 1e-6)
+#define HN_SILENT 1e-20
+
+#pragma clang fp contract(off)
+
+// (s, e) += p, the rounding error of the addition into e
+static __device__ __forceinline__ void hn_add(double& s, double& e, double p) {
+    const double t = s + p, bb = t - s;
+    e += (s - (t - bb)) + (p - bb);
+    s = t;
+}
+
+// (s, e) += a b, the product taken exactly
+static __device__ __forceinline__ void hn_fma(double& s, double& e, double a, double b) {
+    const double p = a * b;
+    e += __builtin_fma(a, b, -p);
+    hn_add(s, e, p);
+}
+
+// The sum of the lanes' (s, e) by a fixed tree, the same on every run.  Every lane gets it; rs / re may be reused after the call.
+static __device__ __forceinline__ double hn_block_sum(double s, double e, double* rs, double* re, int tid) {
+    rs[tid] = s;
+    re[tid] = e;
+    __syncthreads();
+    for (int o = HN_NT / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            double a = rs[tid], b = re[tid];
+            hn_add(a, b, rs[tid + o]);
+            b += re[tid + o];
+            rs[tid] = a;
+            re[tid] = b;
+        }
+        __syncthreads();
+    }
+    const double r = rs[0] + re[0];
+    __syncthreads();
+    return r;
+}
+
+static __host__ __device__ __forceinline__ size_t hn_lds_doubles(int N, int lmax) { return (size_t)N + (size_t)(lmax + 1) + 4 * HN_NT; }
+
+// ------------------------------------------------------------------ one frame
+__global__ void __launch_bounds__(HN_NT) hnr_frames_kernel(const float* __restrict__ y, long ldy, const int32_t* __restrict__ lens,
+                                                           const double* __restrict__ f0, long ldf, const int32_t* __restrict__ frames,
+                                                           const double* __restrict__ w, const double* __restrict__ rw, double fs, int hop,
+                                                           int h, int lmax, double* __restrict__ out, long ldo_b, long ldo_t,
+                                                           int32_t* __restrict__ lag, long ldl, int Tmax) {
+    extern __shared__ double hn_smem[];
+    const int N = 2 * h + 1;
+    double* a = hn_smem;                                                    // [N] the frame, then the windowed frame
+    double* rp = a + N;                                                     // [lmax + 1] r'(tau) of the searched lags
+    double* ps = rp + (lmax + 1);                                           // [HN_NT] the quarters of a lag sum
+    double* pe = ps + HN_NT;
+    double* rs = pe + HN_NT;
+    double* re = rs + HN_NT;
+    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int T = min(frames[b], min(Tmax, HN_MAX_FRAMES));
+    if (t >= T) return;                                                     // the whole workgroup: no barrier is skipped by a part of it
+    const long n = min((long)max(lens[b], 0), ldy);
+    const float* yr = y + (size_t)b * ldy;
+    const long first = (long)t * hop - h;
+    double s = 0.0, e = 0.0;
+    for (int k = tid; k < N; k += HN_NT) {
+        const long i = first + k;
+        const double v = (i >= 0 && i < n) ? (double)yr[i] : 0.0;
+        a[k] = v;
+        hn_add(s, e, v);
+    }
+    const double mu = hn_block_sum(s, e, rs, re, tid) / (double)N;
+    s = 0.0, e = 0.0;
+    for (int k = tid; k < N; k += HN_NT) {                                  // a lane rewrites the entries it wrote
+        const double v = (a[k] - mu) * w[k];
+        a[k] = v;
+        hn_fma(s, e, v, v);
+    }
+    const double r0 = hn_block_sum(s, e, rs, re, tid);                      // its barriers publish a[]
+    double* o = out + (size_t)b * ldo_b + (size_t)t * ldo_t;
+    const double f = f0[(size_t)b * ldf + t];
+    bool valid = f > 0.0 && r0 > HN_SILENT * (double)N;
+    int l0 = 0, l1 = -1;
+    if (valid) {
+        const double tau0 = fs / f;
+        const double lo = fmax(2.0, ceil(tau0 / HN_SEARCH)), hi = fmin((double)(lmax - 1), floor(tau0 * HN_SEARCH));
+        valid = hi >= lo;                                                   // also false for an infinite tau0
+        if (valid) l0 = (int)lo, l1 = (int)hi;
+    }
+    if (!valid) {                                                           // the same for every lane
+        if (tid == 0) {
+            o[0] = 0.0;
+            o[1] = 0.0;
+            o[2] = 0.0;
+            lag[(size_t)b * ldl + t] = 0;
+        }
+        return;
+    }
+    const int base = l0 - 1, nl = l1 - l0 + 3;                              // lags base .. base + nl - 1 <= lmax < N
+    const int wv = tid / HN_WAVE, lane = tid % HN_WAVE;
+    const int Q = (N + HN_WAVES - 1) / HN_WAVES;
+    for (int c0 = 0; c0 < nl; c0 += HN_WAVE) {
+        const int li = c0 + lane, tau = base + li;
+        const int count = li < nl ? N - tau : 0;                            // the terms k = 0 .. N - 1 - tau of this lane's lag
+        const int k1 = min((wv + 1) * Q, N - (base + c0));                  // the longest lag sum of this chunk: the same for the wave
+        s = 0.0, e = 0.0;
+        for (int k = wv * Q; k < k1; ++k)
+            if (k < count) hn_fma(s, e, a[k], a[k + tau]);
+        ps[tid] = s;
+        pe[tid] = e;
+        __syncthreads();
+        if (wv == 0 && li < nl) {
+            double S = ps[lane], E = pe[lane];
+            for (int q = 1; q < HN_WAVES; ++q) {
+                hn_add(S, E, ps[q * HN_WAVE + lane]);
+                E += pe[q * HN_WAVE + lane];
+            }
+            rp[li] = (S + E) / (r0 * rw[tau]);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int best = 1;
+        double rc = rp[1];
+        for (int i = 2; i <= nl - 2; ++i)
+            if (rp[i] > rc) rc = rp[i], best = i;                           // the first maximum over l0 .. l1
+        const double rm = rp[best - 1], rn = rp[best + 1];
+        const double d = rm - 2.0 * rc + rn;
+        const double peak = d < 0.0 ? rc - (rn - rm) * (rn - rm) / (8.0 * d) : rc;
+        const double r = fmin(fmax(peak, HN_R_LO), HN_R_HI);
+        o[0] = r;
+        o[1] = 10.0 * log10(r / (1.0 - r));
+        o[2] = 1.0;
+        lag[(size_t)b * ldl + t] = base + best;
+    }
+}
+
+// ------------------------------------------------------------------ one side
+__global__ void __launch_bounds__(HN_NT) hnr_side_kernel(const double* __restrict__ fr, long ldf_b, long ldf_t,
+                                                         const int32_t* __restrict__ frames, double* __restrict__ stats, long lds, int Tmax) {
+    __shared__ double rs[HN_NT], re[HN_NT];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int T = min(max(frames[b], 0), min(Tmax, HN_MAX_FRAMES));
+    const double* q = fr + (size_t)b * ldf_b;
+    double s = 0.0, e = 0.0, count = 0.0;
+    for (int t = tid; t < T; t += HN_NT) {
+        if (q[(size_t)t * ldf_t + 2] != 0.0) {
+            hn_add(s, e, q[(size_t)t * ldf_t + 1]);
+            count += 1.0;
+        }
+    }
+    const double nv = hn_block_sum(count, 0.0, rs, re, tid);                // small integers: exact
+    double* o = stats + (size_t)b * lds;
+    if (!(nv > 0.0)) {                                                      // the same for every lane
+        if (tid < 3) o[tid] = 0.0;
+        return;
+    }
+    const double m = hn_block_sum(s, e, rs, re, tid) / nv;
+    s = 0.0, e = 0.0;
+    for (int t = tid; t < T; t += HN_NT) {
+        if (q[(size_t)t * ldf_t + 2] != 0.0) {
+            const double d = q[(size_t)t * ldf_t + 1] - m;
+            hn_fma(s, e, d, d);
+        }
+    }
+    const double m2 = hn_block_sum(s, e, rs, re, tid);
+    if (tid == 0) {
+        o[0] = nv;
+        o[1] = m;
+        o[2] = m2;
+    }
+}
+
+// ------------------------------------------------------------------ the sums along the path
+__global__ void __launch_bounds__(HN_NT) hnr_on_path_kernel(const int32_t* __restrict__ pi, const int32_t* __restrict__ pj, long ldq,
+                                                            const int32_t* __restrict__ plen, const double* __restrict__ fa, long lda_b,
+                                                            long lda_t, const double* __restrict__ fb, long ldb_b, long ldb_t,
+                                                            const int32_t* __restrict__ alens, const int32_t* __restrict__ blens,
+                                                            double* __restrict__ sums, long ldo, int T1max, int T2max) {
+    __shared__ double rs[HN_NT], re[HN_NT];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int T1 = min(alens[p], min(T1max, HN_MAX_FRAMES)), T2 = min(blens[p], min(T2max, HN_MAX_FRAMES));
+    const int P = (int)min((long)max(plen[p], 0), ldq);
+    const int32_t* qi = pi + (size_t)p * ldq;
+    const int32_t* qj = pj + (size_t)p * ldq;
+    const double* a = fa + (size_t)p * lda_b;
+    const double* bq = fb + (size_t)p * ldb_b;
+    double sx = 0.0, ex = 0.0, sy = 0.0, ey = 0.0, count = 0.0;
+    for (int k = tid; k < P; k += HN_NT) {
+        const int i = qi[k], j = qj[k];
+        if (i < 0 || i >= T1 || j < 0 || j >= T2) continue;                 // a path entry outside the pair is skipped, never followed
+        const double* u = a + (size_t)i * lda_t;
+        const double* v = bq + (size_t)j * ldb_t;
+        if (u[2] == 0.0 || v[2] == 0.0) continue;
+        hn_add(sx, ex, u[1]);
+        hn_add(sy, ey, v[1]);
+        count += 1.0;
+    }
+    const double n = hn_block_sum(count, 0.0, rs, re, tid);
+    double* o = sums + (size_t)p * ldo;
+    if (!(n > 0.0)) {                                                       // the same for every lane
+        if (tid < 7) o[tid] = 0.0;
+        return;
+    }
+    const double xm = hn_block_sum(sx, ex, rs, re, tid) / n, ym = hn_block_sum(sy, ey, rs, re, tid) / n;
+    double sxx = 0.0, exx = 0.0, syy = 0.0, eyy = 0.0, sxy = 0.0, exy = 0.0, sd2 = 0.0, ed2 = 0.0;
+    for (int k = tid; k < P; k += HN_NT) {
+        const int i = qi[k], j = qj[k];
+        if (i < 0 || i >= T1 || j < 0 || j >= T2) continue;
+        const double* u = a + (size_t)i * lda_t;
+        const double* v = bq + (size_t)j * ldb_t;
+        if (u[2] == 0.0 || v[2] == 0.0) continue;
+        const double x = u[1], yv = v[1];
+        const double dx = x - xm, dy = yv - ym, dd = x - yv;
+        hn_fma(sxx, exx, dx, dx);
+        hn_fma(syy, eyy, dy, dy);
+        hn_fma(sxy, exy, dx, dy);
+        hn_fma(sd2, ed2, dd, dd);
+    }
+    const double r0 = hn_block_sum(sxx, exx, rs, re, tid), r1 = hn_block_sum(syy, eyy, rs, re, tid);
+    const double r2 = hn_block_sum(sxy, exy, rs, re, tid), r3 = hn_block_sum(sd2, ed2, rs, re, tid);
+    if (tid == 0) {
+        o[0] = n;
+        o[1] = xm;
+        o[2] = ym;
+        o[3] = r0;
+        o[4] = r1;
+        o[5] = r2;
+        o[6] = r3;
+    }
+}
+
+// ------------------------------------------------------------------ the C ABI
+extern "C" int fs2_hnr_max_window(void) { return HN_MAX_WINDOW; }
+
+extern "C" int fs2_hnr_frames(const float* y, long ldy, const int32_t* lens, const double* f0, long ldf, const int32_t* frames,
+                              const double* w, const double* rw, double fs, int hop, int h, int lmax, double* out, long ldo_b, long ldo_t,
+                              int32_t* lag, long ldl, int B, int Tmax, hipStream_t stream) {
+    FS2_CHECK_ARG(B >= 0 && Tmax >= 1 && Tmax <= HN_MAX_FRAMES, "hnr_frames: bad shape B=%d Tmax=%d (1..%d frames)", B, Tmax, HN_MAX_FRAMES);
+    FS2_CHECK_ARG(B <= 65535, "hnr_frames: %d rows, supported are at most 65535 per launch", B);
+    FS2_CHECK_ARG(h >= 1 && 2 * (long)h + 1 <= HN_MAX_WINDOW, "hnr_frames: a window of 2 * %d + 1 samples, supported are 3..%d", h, HN_MAX_WINDOW);
+    const int N = 2 * h + 1;
+    FS2_CHECK_ARG(lmax >= 3 && lmax < N, "hnr_frames: the longest lag %d is not in 3..%d, below the window", lmax, N - 1);
+    FS2_CHECK_ARG(fs > 0.0 && fs < 1e9 && hop >= 1 && hop <= (1 << 20), "hnr_frames: bad rates fs=%g hop=%d", fs, hop);
+    FS2_CHECK_ARG(ldy >= 1 && ldf >= Tmax && ldo_t >= 3 && ldo_b >= (long)Tmax * ldo_t && ldl >= Tmax,
+                  "hnr_frames: bad strides y %ld f0 %ld out %ld %ld lag %ld", ldy, ldf, ldo_b, ldo_t, ldl);
+    const size_t lds = hn_lds_doubles(N, lmax) * sizeof(double);
+    FS2_CHECK_ARG(lds <= HN_MAX_LDS, "hnr_frames: %zu bytes of LDS, more than %d", lds, HN_MAX_LDS);
+    if (B == 0) return FS2_OK;
+    FS2_CHECK_ARG(y && lens && f0 && frames && w && rw && out && lag, "hnr_frames: null pointer");
+    static Fs2DevOnce once;
+    once.run([&] { (void)hipFuncSetAttribute((const void*)hnr_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HN_MAX_LDS); });
+    hnr_frames_kernel<<<dim3(Tmax, B), HN_NT, lds, stream>>>(y, ldy, lens, f0, ldf, frames, w, rw, fs, hop, h, lmax, out, ldo_b, ldo_t, lag,
+                                                             ldl, Tmax);
+    FS2_CHECK_LAUNCH("hnr_frames");
+    return FS2_OK;
+}
+
+extern "C" int fs2_hnr_side(const double* fr, long ldf_b, long ldf_t, const int32_t* frames, double* stats, long lds, int B, int Tmax,
+                            hipStream_t stream) {
+    FS2_CHECK_ARG(B >= 0 && Tmax >= 1 && Tmax <= HN_MAX_FRAMES, "hnr_side: bad shape B=%d Tmax=%d (1..%d frames)", B, Tmax, HN_MAX_FRAMES);
+    FS2_CHECK_ARG(ldf_t >= 3 && ldf_b >= (long)Tmax * ldf_t && lds >= 3, "hnr_side: bad strides frames %ld %ld stats %ld", ldf_b, ldf_t, lds);
+    if (B == 0) return FS2_OK;
+    FS2_CHECK_ARG(fr && frames && stats, "hnr_side: null pointer");
+    hnr_side_kernel<<<B, HN_NT, 0, stream>>>(fr, ldf_b, ldf_t, frames, stats, lds, Tmax);
+    FS2_CHECK_LAUNCH("hnr_side");
+    return FS2_OK;
+}
+
+extern "C" int fs2_hnr_on_path(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* plen, const double* fr_ref, long lda_b,
+                               long lda_t, const double* fr_syn, long ldb_b, long ldb_t, const int32_t* alens, const int32_t* blens,
+                               double* sums, long ldo, int B, int T1max, int T2max, hipStream_t stream) {
+    FS2_CHECK_ARG(B >= 0 && T1max >= 1 && T2max >= 1 && T1max <= HN_MAX_FRAMES && T2max <= HN_MAX_FRAMES,
+                  "hnr_on_path: bad shape B=%d T1max=%d T2max=%d (1..%d frames)", B, T1max, T2max, HN_MAX_FRAMES);
+    FS2_CHECK_ARG(ldq >= 0 && lda_t >= 3 && lda_b >= (long)T1max * lda_t && ldb_t >= 3 && ldb_b >= (long)T2max * ldb_t && ldo >= 7,
+                  "hnr_on_path: bad strides path %ld ref %ld %ld syn %ld %ld sums %ld", ldq, lda_b, lda_t, ldb_b, ldb_t, ldo);
+    if (B == 0) return FS2_OK;
+    FS2_CHECK_ARG(pi && pj && plen && fr_ref && fr_syn && alens && blens && sums, "hnr_on_path: null pointer");
+    hnr_on_path_kernel<<<B, HN_NT, 0, stream>>>(pi, pj, ldq, plen, fr_ref, lda_b, lda_t, fr_syn, ldb_b, ldb_t, alens, blens, sums, ldo,
+                                                T1max, T2max);
+    FS2_CHECK_LAUNCH("hnr_on_path");
+    return FS2_OK;
+}

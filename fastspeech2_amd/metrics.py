@@ -84,6 +84,14 @@ cwt_power_ratio_db, lf0_mean_ref, lf0_mean_syn, lf0_std_ref and lf0_std_syn, the
 the other F0 numbers (`f0_estimator`).  Without `wavelet` every launch, every row and the summary are what they are without this
 paragraph.
 
+Harmonics-to-noise ratio (`hnr=True`, `score.py --hnr`; needs F0, not `prosody`).  How much of each voiced frame's power repeats at
+the pitch period (Boersma 1993), the measure of a hoarse, buzzy or noisy voice, taken of both sides' audio at the lags around the
+scored F0 track (`f0_estimator`) and compared per side and along the cepstral path, specified in full in the docstring of `hnr`:
+every row also carries hnr_mean_db_ref, hnr_mean_db_syn, hnr_std_db_ref, hnr_std_db_syn, hnr_frames_ref, hnr_frames_syn, hnr_cells,
+hnr_diff_db, hnr_rmse_db and hnr_corr, the summary the frame-weighted hnr_mean_db_ref / _syn with hnr_frames_ref / _syn, hnr_cells,
+the cell-weighted hnr_diff_db and hnr_rmse_db, hnr_corr_mean with hnr_corr_nan_utterances, and hnr_unscored_utterances.  Without
+`hnr` every launch, every row and the summary are what they are without this paragraph.
+
 Storage.  The local costs and backpointers of a pair are held skewed, cell (i, j) at row (i + j) mod T2, column i of a (T2max, T1max)
 matrix: an anti-diagonal is contiguous, the buffer is no larger than the plain one (`unskew` undoes it for a test).  The accumulated
 costs never leave the chip.  Determinism: no atomics, sums in a fixed order; two runs give byte-identical scores.
@@ -105,6 +113,7 @@ PROSODY_FRAME_BYTES = 24                                    # per frame: the com
 CORR_FLOOR = 1e-24
 SMOOTHING_BANDS = 8                                         # at most: the bands of `modspec.EDGES_HZ`
 WAVELET_FRAME_BYTES = 88                                    # per frame and side: z and the ten scales of its transform, float64
+HNR_FRAME_BYTES = 28                                        # per frame and side: r, hnr, valid in float64 and the lag in int32
 PROSODY_SCORES = ("gpe", "ffe", "f0_corr", "f0_dtw_hz", "energy_mae", "energy_mae_rel")
 
 
@@ -465,18 +474,22 @@ def summarize(rows):
     if "cwt_corr" in rows[0]:
         from . import cwt as Cwt
         out.update(Cwt.summarize(rows))
+    if "hnr_cells" in rows[0]:
+        from . import hnr as Hnr
+        out.update(Hnr.summarize(rows))
     return out
 
 
-def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0, prosody=False, smoothing=False, wavelet=False):
+def batch_bytes(n, T1, T2, n_mcep=13, hop_length=256, fft_size=0, prosody=False, smoothing=False, wavelet=False, hnr=False):
     """What a batch of n pairs padded to (T1, T2) frames holds on the device: 9 B per (i, j) cell (local cost + backpointer), the
     audio, its STFT workspace and mel (about 40 B per sample), cepstra, F0 and the path; with `fft_size` (cepstra="world") also the
     spectral envelope, fft_size / 2 + 1 float64 bins per frame and side; with `prosody` the compacted contours and the second path
     (24 B per frame; the contour DTW's cells reuse the first DTW's, released by then); with `smoothing` the moments and band values
     of both sides, (2 + SMOOTHING_BANDS) float64 per coefficient and side; with `wavelet` the normalised contour and the ten scales
-    of its transform, 88 B per frame and side."""
+    of its transform, 88 B per frame and side; with `hnr` r, hnr, valid and the lag of every frame, 28 B per frame and side."""
     return n * (T1 * T2 * CELL_BYTES + (T1 + T2) * (hop_length * 40 + n_mcep * 8 + 64 + (fft_size // 2 + 1) * 8 * (fft_size > 0)
-                                                    + PROSODY_FRAME_BYTES * bool(prosody) + WAVELET_FRAME_BYTES * bool(wavelet))
+                                                    + PROSODY_FRAME_BYTES * bool(prosody) + WAVELET_FRAME_BYTES * bool(wavelet)
+                                                    + HNR_FRAME_BYTES * bool(hnr))
                 + 2 * n_mcep * (2 + SMOOTHING_BANDS) * 8 * bool(smoothing))
 
 
@@ -498,7 +511,7 @@ def frame_counts(n_samples, sampling_rate, hop_length, f0=True):
 
 
 def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None, f0=True, device="cuda", budget=4 << 30,
-                cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", smoothing=False, wavelet=False):
+                cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", smoothing=False, wavelet=False, hnr=False):
     """Scores of (recorded, synthesized) pairs of float32 waveforms at `sampling_rate` -> one dict per pair (module docstring), in
     the order given.  `stft` is the config's `audio.TacotronSTFT`.  Pairs are packed longest first into ragged batches under `budget`
     bytes of device buffers; per batch: both sides through one pinned staging buffer, mel -> cepstra -> local cost -> scan ->
@@ -515,8 +528,11 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
     `budget`.  With `smoothing` the two kernels of `modspec` run on both sides' cepstra, whichever they are, before these are
     released, their results ride in the batch's one D2H copy, and every row also carries the over-smoothing keys of the module
     docstring.  With `wavelet` (needs `f0`) the three kernels of `cwt` run on both sides' scored F0 track, the path stays alive until
-    the path sums are taken, the results ride in the same D2H copy, and every row also carries the wavelet keys."""
+    the path sums are taken, the results ride in the same D2H copy, and every row also carries the wavelet keys.  With `hnr` (needs `f0`) the two
+    per-side kernels of `hnr` run on each side's audio and scored F0 track while the audio is on the device, the path kernel before
+    the path is released, the results ride in the same D2H copy, and every row also carries the HNR keys."""
     from . import cwt as Cwt
+    from . import hnr as Hnr
     from . import envelope as Env
     from . import modspec as Modspec
     if f0_estimator not in ("dio", "pyin"):
@@ -527,6 +543,10 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
         raise ValueError("wavelet prosody scores need F0: wavelet=True cannot go with f0=False")
     if wavelet:
         Cwt.scales(sampling_rate, hop_length)                               # a hop above 20 ms is refused before any work
+    if hnr and not f0:
+        raise ValueError("the harmonics-to-noise ratio needs F0: hnr=True cannot go with f0=False")
+    if hnr:
+        Hnr.window(sampling_rate)                                           # a rate whose window does not fit is refused before any work
     if prosody and stft is None:
         raise ValueError("prosody scores need the STFT for the frame energy: stft=None cannot go with prosody=True")
     if cepstra not in ("mel", "world"):
@@ -575,19 +595,20 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
         mel = energy = None
         if prosody or not world:
             mel, energy, _ = stft.mel_spectrogram_ragged(y.clamp(-1.0, 1.0), lens)
+        harm = Hnr.measure(y, lens, scored, frames, sampling_rate, hop_length) if hnr else None
         if world:
-            return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), scored if f0 else None, energy
-        return cepstra_fn(mel, frames, n_mcep), scored, energy
+            return Env.world_cepstra(y, lens, track, frames, sampling_rate, frame_period, n_mcep, alpha), scored if f0 else None, energy, harm
+        return cepstra_fn(mel, frames, n_mcep), scored, energy, harm
 
-    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody, smoothing, wavelet)     # noqa: E731
+    cost = lambda n, T1, T2: batch_bytes(n, T1, T2, n_mcep, hop_length, fft_size, prosody, smoothing, wavelet, hnr)     # noqa: E731
     if f0 and f0_estimator == "pyin":                                       # one side's pYIN chunk workspace lives at a time
         from . import pyin as Pyin
         cepstral = cost
         cost = lambda n, T1, T2: cepstral(n, T1, T2) + Pyin.workspace_bytes(n, max(T1, T2))     # noqa: E731
     for batch in ragged.greedy_batches(list(zip(fr, fs)), budget, cost):
         al, bl = [fr[i] for i in batch], [fs[i] for i in batch]
-        a, f0a, ea = side([ref_wavs[i] for i in batch], al)
-        b, f0b, eb = side([syn_wavs[i] for i in batch], bl)
+        a, f0a, ea, ha = side([ref_wavs[i] for i in batch], al)
+        b, f0b, eb, hb = side([syn_wavs[i] for i in batch], bl)
         total, plen, pi, pj = dtw(a, al, b, bl)
         smooth = [v.reshape(len(batch), -1) for v in Modspec.measure(a, al, bins) + Modspec.measure(b, bl, bins)] if smoothing else []
         del a, b
@@ -599,6 +620,10 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
             Wb, pwb, stb = Cwt.measure(f0b, bl, sampling_rate, hop_length)
             smooth += [Cwt.on_path(pi, pj, plen, Wa, al, Wb, bl).reshape(len(batch), -1), pwa, sta, pwb, stb]
             del Wa, Wb
+        n_wave = sum(v.shape[1] for v in smooth) - (2 * n_mcep * (1 + len(bins)) if smoothing else 0)
+        if hnr:                                                             # before the path is released below
+            smooth += [Hnr.on_path(pi, pj, plen, ha[0], al, hb[0], bl), ha[1], hb[1]]
+            del ha, hb
         if prosody:
             cols += list(prosody_on_path(pi, pj, plen, f0a, al, f0b, bl, ea, eb).unbind(1))
             del pi, pj
@@ -618,8 +643,12 @@ def score_pairs(ref_wavs, syn_wavs, stft, sampling_rate, hop_length, n_mcep=None
                 m2a, ba, m2b, bb = np.split(host[r, n_cols:n_cols + n_smooth], np.cumsum([n_mcep, n_mcep * len(bins), n_mcep])[:3])
                 rows[i].update(Modspec.row_scores(m2a, ba.reshape(n_mcep, -1), al[r], m2b, bb.reshape(n_mcep, -1), bl[r]))
             if wavelet:
-                ws, pwa, sta, pwb, stb = np.split(host[r, n_cols + n_smooth:], np.cumsum([Cwt.COMPONENTS * 4, Cwt.SCALES, 4, Cwt.SCALES]))
+                ws, pwa, sta, pwb, stb = np.split(host[r, n_cols + n_smooth:n_cols + n_smooth + n_wave],
+                                                  np.cumsum([Cwt.COMPONENTS * 4, Cwt.SCALES, 4, Cwt.SCALES]))
                 rows[i].update(Cwt.row_scores(ws, host[r, 1], pwa, al[r], sta, pwb, bl[r], stb))
+            if hnr:
+                hs, hsa, hsb = np.split(host[r, n_cols + n_smooth + n_wave:], np.cumsum([Hnr.PATH_SUMS, Hnr.SIDE_STATS]))
+                rows[i].update(Hnr.row_scores(hs, hsa, hsb))
             if world:
                 rows[i].update(cepstra="world", alpha=alpha, fft_size=fft_size)
             if f0 and f0_estimator != "dio":
@@ -683,7 +712,7 @@ class _Rates:
 
 def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, trim=True, f0=True, n_mcep=None, score_fn=None,
         device="cuda", cepstra="mel", alpha=None, prosody=False, f0_estimator="dio", aligned=False, max_len_diff=None, aligned_fn=None,
-        smoothing=False, wavelet=False):
+        smoothing=False, wavelet=False, hnr=False):
     """score.py: pair, trim, score, write one JSON object per utterance to `out_path`.  `score_fn(ref_wavs, syn_wavs) -> [dict]`
     replaces the device stage (called with `prosody=True` as a keyword when that is asked for).  Returns (rows, skipped, summary).
     With cepstra="world" the rows and the summary also say cepstra, alpha and fft_size; with "mel" they are what they were before
@@ -698,7 +727,8 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
     the over-smoothing keys of `modspec` to every row and to the summary, with ms_bands_hz, the band edges in Hz at this config's
     frame rate; a `score_fn` is then called with `smoothing=True` as a keyword.  `wavelet` (score.py --wavelet) adds the wavelet
     prosody keys of `cwt` to every row and to the summary, is refused with f0=False before a file is read, and reaches a `score_fn`
-    as `wavelet=True`."""
+    as `wavelet=True`.  `hnr` (score.py --hnr) adds the harmonics-to-noise keys of `hnr` to every row and to the summary, is refused with
+    f0=False before a file is read, and reaches a `score_fn` as `hnr=True`."""
     import json
     pp = config["preprocessing"]
     sr, hop = pp["audio"]["sampling_rate"], pp["stft"]["hop_length"]
@@ -711,6 +741,11 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
     if wavelet:
         from . import cwt as Cwt
         Cwt.scales(sr, hop)                                                 # refused before a file is read
+    if hnr and not f0:
+        raise ValueError("--hnr needs F0 and cannot go with --no_f0")
+    if hnr:
+        from . import hnr as Hnr
+        Hnr.window(sr)                                                      # refused before a file is read
     world_keys = {}
     if cepstra == "world":                                                  # refused before a file is read
         from . import envelope as Env
@@ -739,9 +774,10 @@ def run(config, result_path, source, out_path=None, syn_dir=None, ref_dir=None, 
                                   pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
         score_fn = lambda r, s: score_pairs(r, s, stft, sr, hop, n_mcep=n_mcep, f0=f0, device=device, cepstra=cepstra,     # noqa: E731
                                             alpha=alpha, prosody=prosody, f0_estimator=f0_estimator, smoothing=smoothing,
-                                            wavelet=wavelet)
-    elif prosody or smoothing or wavelet:
-        given, asked = score_fn, {k: True for k, v in (("prosody", prosody), ("smoothing", smoothing), ("wavelet", wavelet)) if v}
+                                            wavelet=wavelet, hnr=hnr)
+    elif prosody or smoothing or wavelet or hnr:
+        given, asked = score_fn, {k: True for k, v in (("prosody", prosody), ("smoothing", smoothing), ("wavelet", wavelet),
+                                                       ("hnr", hnr)) if v}
         score_fn = lambda r, s: given(r, s, **asked)                         # noqa: E731
     scores = score_fn([it["ref"] for it in items], [it["syn"] for it in items]) if items else []
     rows = [{"basename": it["basename"], "speaker": it["speaker"], "reference_window": it["window"], **sc}

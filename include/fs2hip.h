@@ -746,6 +746,35 @@ int fs2_cwt_on_path(const int32_t* pi, const int32_t* pj, long ldq, const int32_
                     const double* w_syn, long lds_b, long lds_i, const int32_t* alens, const int32_t* blens, double* sums, long ldo_b,
                     long ldo_c, int B, int T1max, int T2max, fs2_stream_t stream);
 
+/* ---- harmonics-to-noise ratio (csrc/fs2_hnr.hip; specification: fastspeech2_amd/hnr.py) ----
+ * Ragged batches: row b of the float32 audio y [B][ldy] has lens[b] samples and frames[b] frames (int32, device), 1 <= Tmax <=
+ * fs2_dtw_max_frames().  fp64 after the load; no atomics, every sum carries its rounding errors in a second word and has one order:
+ * the same input gives the same bytes, whatever rows are beside it.  Nothing at a frame >= frames[b] is read or written, no sample
+ * >= lens[b] is read.
+ * fs2_hnr_max_window: the longest window N = 2 h + 1 in samples, 8191. */
+int fs2_hnr_max_window(void);
+/* Frame t < frames[b] of row b: x[k] = y[b][t hop - h + k], k < N = 2 h + 1, 0 outside [0, lens[b]); mu = (sum x) / N, a[k] = (x[k] -
+ * mu) w[k], r0 = sum a^2, with w [N] and rw [lmax + 1] the caller's device tables (the window and its normalised autocorrelation).
+ * With f = f0[b][t] (f0 [B][ldf] f64, Hz): the frame is invalid, out[b][t][0..3) = 0 and lag[b][t] = 0, when f is not above 0, r0 <=
+ * 1e-20 N, or l1 < l0 for tau0 = fs / f, l0 = max(2, ceil(tau0 / 1.2)), l1 = min(lmax - 1, floor(tau0 * 1.2)).  Otherwise r'(tau) =
+ * (sum_{k < N - tau} a[k] a[k + tau]) / (r0 rw[tau]) for tau in [l0 - 1, l1 + 1], lag[b][t] = the first tau in [l0, l1] that
+ * maximises it, the peak of the parabola through its two neighbours (r' itself when the second difference d is not below 0: r' -
+ * (r'(tau + 1) - r'(tau - 1))^2 / (8 d)), r = that clipped to [1e-3, 1 - 1e-6], and out[b][t] = {r, 10 log10(r / (1 - r)), 1}.
+ * 3 <= N <= fs2_hnr_max_window(), 3 <= lmax < N, hop >= 1; strides ldf, ldl >= Tmax, ldo_t >= 3, ldo_b >= Tmax ldo_t; B <= 65535. */
+int fs2_hnr_frames(const float* y, long ldy, const int32_t* lens, const double* f0, long ldf, const int32_t* frames, const double* w,
+                   const double* rw, double fs, int hop, int h, int lmax, double* out, long ldo_b, long ldo_t, int32_t* lag, long ldl, int B,
+                   int Tmax, fs2_stream_t stream);
+/* stats[b][0..3) = {n, mean, M2}: the number of frames t < frames[b] of fr (as fs2_hnr_frames writes it) with fr[b][t][2] != 0, the
+ * mean of their fr[b][t][1] and, in a second pass, the sum of the squared differences from it; all 0 without such a frame.  lds >= 3. */
+int fs2_hnr_side(const double* fr, long ldf_b, long ldf_t, const int32_t* frames, double* stats, long lds, int B, int Tmax,
+                 fs2_stream_t stream);
+/* Along the path (pi, pj, plen as fs2_dtw_backtrack writes them), over the cells whose frames pi[k] of fr_ref and pj[k] of fr_syn
+ * (both as fs2_hnr_frames writes them) are both valid, with x, y their two hnr values: sums[p][0..7) = {cells, mean x, mean y, Sxx,
+ * Syy, Sxy about those means of a first pass, Sd2 = sum (x - y)^2}; all 0 for a pair without such a cell.  ldo >= 7. */
+int fs2_hnr_on_path(const int32_t* pi, const int32_t* pj, long ldq, const int32_t* plen, const double* fr_ref, long lda_b, long lda_t,
+                    const double* fr_syn, long ldb_b, long ldb_t, const int32_t* alens, const int32_t* blens, double* sums, long ldo, int B,
+                    int T1max, int T2max, fs2_stream_t stream);
+
 /* ---- time-aligned intelligibility: STOI and ESTOI (csrc/fs2_stoi.hip; specification: fastspeech2_amd/stoi.py) ----
  * Ragged batches of time-aligned pairs at 10 kHz: float32 rows x (clean) and y (B, ldx) sharing one device lens, fp64 after the load,
  * no atomics, fixed-order sums: the same input gives the same bytes.  Nothing at or beyond lens[b] is read.  Frames of 256 samples at

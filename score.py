@@ -3,7 +3,7 @@
 
     python score.py -p preprocess.yaml -t train.yaml --source val.txt [--syn_dir DIR] [--ref_dir DIR] [--no_trim] [--no_f0]
                     [--cepstra {mel,world}] [--alpha A] [--n_mcep K] [--prosody] [--f0 {dio,pyin}] [--aligned] [--max_len_diff N]
-                    [--smoothing] [--wavelet] [--out scores.jsonl]
+                    [--smoothing] [--wavelet] [--hnr] [--out scores.jsonl]
 
 For every `basename|speaker|...` line of `--source` the recorded `{raw_path}/{speaker}/{basename}.wav` (or `{ref_dir}/{basename}.wav`)
 is compared with `{result_path}/{basename}.wav` (or `{syn_dir}/...`), where `synthesize.py --mode batch` writes: mel-cepstral
@@ -33,7 +33,13 @@ the summary also say at which time scale the pitch contour departs from the reco
 interpolated over the unvoiced frames, taken as ln F0 and normalised per utterance, transformed by a Mexican-hat wavelet at ten
 scales from 20 ms to 10.24 s, and the two transforms are correlated along the DTW path, per scale and per level of two adjacent
 scales, with the power per scale of each side and the mean and deviation of ln F0.  The constants are FastSpeech 2's pitch
-spectrogram's as remembered, not checked against the papers; the numbers compare runs of this tool."""
+spectrogram's as remembered, not checked against the papers; the numbers compare runs of this tool.
+With `--hnr` (not with `--no_f0`; it goes with either `--f0` and either `--cepstra`) every row and the summary also say how clean
+the voiced speech of both sides is (fastspeech2_amd/hnr.py): the harmonics-to-noise ratio of Boersma (1993) in dB per voiced frame,
+from the window-corrected autocorrelation at the lags around the scored F0, its mean and deviation per side, and its difference
+(synthesized minus reference), RMSE and correlation along the DTW path.  A periodic signal in white noise at S dB SNR scores S dB.
+Agreement with Praat is unmeasured, and a higher value is not claimed to be better: the numbers compare the two sides and runs of
+this tool."""
 import argparse
 import json
 import sys
@@ -71,6 +77,8 @@ def parse_args(argv=None):
     parser.add_argument("--wavelet", action="store_true",
                         help="also the wavelet prosody scores: correlation, RMSE and power of the continuous ln F0 at ten time scales "
                              "(needs F0)")
+    parser.add_argument("--hnr", action="store_true",
+                        help="also the harmonics-to-noise ratio of both sides' voiced frames, per side and along the path (needs F0)")
     parser.add_argument("--out", type=str, default="scores.jsonl")
     parser.add_argument("--device", type=str, default="cuda")
     return parser.parse_args(argv)
@@ -86,7 +94,7 @@ def main(argv=None, score_fn=None, aligned_fn=None):
                                              score_fn=score_fn, device=args.device, cepstra=args.cepstra, alpha=args.alpha,
                                              prosody=args.prosody, f0_estimator=args.f0, aligned=args.aligned,
                                              max_len_diff=args.max_len_diff, aligned_fn=aligned_fn, smoothing=args.smoothing,
-                                             wavelet=args.wavelet)
+                                             wavelet=args.wavelet, hnr=args.hnr)
     except ValueError as e:
         sys.exit(str(e))
     for name, reason in skipped:
