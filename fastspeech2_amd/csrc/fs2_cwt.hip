@@ -3,10 +3,9 @@
 // transforms along a DTW path.  fp64, ragged batches of rows of at most 2048 frames.  The specification is the docstring of
 // fastspeech2_amd/cwt.py; tests/cwt_ref.py restates it in numpy (explicit loops, an FFT convolution).
 //
-// Every sum here carries its rounding errors in a second word (the two-sum of Knuth for the additions, an fma for the error of
-// each product), per lane in ascending order and then over the 256 lanes by a fixed tree: the result is the sum of the exactly
-// evaluated terms rounded once, except in cases too rare to meet.  No atomics; nothing at a frame >= lens[b] is read or written;
-// the same input gives the same bytes, and a row's bytes do not depend on the rows beside it (a workgroup sees one row only).
+// Every sum here is a compensated sum of fs2_comp.h, per lane in ascending order and then over the 256 lanes by its fixed tree.  No
+// atomics; nothing at a frame >= lens[b] is read or written; the same input gives the same bytes, and a row's bytes do not depend
+// on the rows beside it (a workgroup sees one row only).
 //
 //   fs2_cwt_contour    one workgroup per row, the row in LDS.  x = ln f0 at the voiced frames (f0 > 0).  The previous and the next
 //                      voiced frame of every frame are an inclusive forward max-scan of (voiced ? t : -1) and a backward min-scan of
@@ -20,7 +19,7 @@
 //                      bound by arithmetic, which the four waves of a workgroup (several workgroups fit a CU) keep issued.
 //   fs2_cwt_on_path    one workgroup per (pair, component): component c < 10 is scale c, component 10 + j the level W_2j + W_2j+1
 //                      (0-based), formed at every path cell.  A first pass for the two means, a second for Sxx, Syy, Sxy, Sd2.
-#include "fs2_common.h"
+#include "fs2_comp.h"
 
 #define CW_MAX_FRAMES 2048          // = fs2_dtw_max_frames()
 #define CW_NT 256
@@ -34,40 +33,6 @@ struct CwSupport {
 };
 
 #pragma clang fp contract(off)
-
-// (s, e) += p, the rounding error of the addition into e
-static __device__ __forceinline__ void cw_add(double& s, double& e, double p) {
-    const double t = s + p, bb = t - s;
-    e += (s - (t - bb)) + (p - bb);
-    s = t;
-}
-
-// (s, e) += a b, the product taken exactly
-static __device__ __forceinline__ void cw_fma(double& s, double& e, double a, double b) {
-    const double p = a * b;
-    e += __builtin_fma(a, b, -p);
-    cw_add(s, e, p);
-}
-
-// The sum of the lanes' (s, e) by a fixed tree, the same on every run.  Every lane gets it; rs / re may be reused after the call.
-static __device__ __forceinline__ double cw_block_sum(double s, double e, double* rs, double* re, int tid) {
-    rs[tid] = s;
-    re[tid] = e;
-    __syncthreads();
-    for (int o = CW_NT / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            double a = rs[tid], b = re[tid];
-            cw_add(a, b, rs[tid + o]);
-            b += re[tid + o];
-            rs[tid] = a;
-            re[tid] = b;
-        }
-        __syncthreads();
-    }
-    const double r = rs[0] + re[0];
-    __syncthreads();
-    return r;
-}
 
 static __device__ __forceinline__ int cw_len(const int32_t* lens, int b, int Tmax) { return min(lens[b], min(Tmax, CW_MAX_FRAMES)); }
 
@@ -104,7 +69,7 @@ __global__ void __launch_bounds__(CW_NT) cwt_contour_kernel(const double* __rest
         }
         __syncthreads();
     }
-    const double nv = cw_block_sum(count, 0.0, rs, re, tid);                // small integers: exact
+    const double nv = cs_block_sum<CW_NT>(count, 0.0, rs, re, tid);         // small integers: exact
     double m = 0.0, sd = 0.0;
     if (nv > 0.0) {                                                         // the same for every lane
         for (int t = tid; t < T; t += CW_NT) {
@@ -124,14 +89,14 @@ __global__ void __launch_bounds__(CW_NT) cwt_contour_kernel(const double* __rest
         }
         __syncthreads();
         double s = 0.0, e = 0.0;
-        for (int t = tid; t < T; t += CW_NT) cw_add(s, e, x[t]);
-        m = cw_block_sum(s, e, rs, re, tid) / (double)T;
+        for (int t = tid; t < T; t += CW_NT) cs_add(s, e, x[t]);
+        m = cs_block_sum<CW_NT>(s, e, rs, re, tid) / (double)T;
         s = 0.0, e = 0.0;
         for (int t = tid; t < T; t += CW_NT) {
             const double d = x[t] - m;
-            cw_fma(s, e, d, d);
+            cs_fma(s, e, d, d);
         }
-        sd = sqrt(cw_block_sum(s, e, rs, re, tid) / (double)T);
+        sd = sqrt(cs_block_sum<CW_NT>(s, e, rs, re, tid) / (double)T);
     }
     const bool flat = !(nv > 0.0) || !(sd > CW_FLAT_SD);
     double* zr = z + (size_t)b * ldz;
@@ -171,15 +136,15 @@ __global__ void __launch_bounds__(CW_NT) cwt_transform_kernel(const double* __re
         for (int d = dlo; d <= dhi; ++d) {
             const int u = t + d;
             const double zv = (u >= 0 && u < T) ? zs[u] : 0.0;
-            cw_fma(s, e, zv, ts[d < 0 ? -d : d]);
+            cs_fma(s, e, zv, ts[d < 0 ? -d : d]);
         }
         if (t < T) {
             const double w = s + e;
             wr[t] = w;
-            cw_fma(ps, pe, w, w);
+            cs_fma(ps, pe, w, w);
         }
     }
-    const double total = cw_block_sum(ps, pe, rs, re, tid);
+    const double total = cs_block_sum<CW_NT>(ps, pe, rs, re, tid);
     if (tid == 0) power[(size_t)b * ldp + i] = total;
 }
 
@@ -206,30 +171,30 @@ __global__ void __launch_bounds__(CW_NT) cwt_on_path_kernel(const int32_t* __res
         const int i = qi[k], j = qj[k];
         if (i < 0 || i >= T1 || j < 0 || j >= T2) continue;                 // a path entry outside the pair is skipped, never followed
         const double x = level ? a0[i] + a1[i] : a0[i], y = level ? b0[j] + b1[j] : b0[j];
-        cw_add(sx, ex, x);
-        cw_add(sy, ey, y);
+        cs_add(sx, ex, x);
+        cs_add(sy, ey, y);
         count += 1.0;
     }
-    const double n = cw_block_sum(count, 0.0, rs, re, tid);
+    const double n = cs_block_sum<CW_NT>(count, 0.0, rs, re, tid);
     double* o = sums + (size_t)p * ldo_b + (size_t)comp * ldo_c;
     if (!(n > 0.0)) {                                                       // the same for every lane
         if (tid < 4) o[tid] = 0.0;
         return;
     }
-    const double xm = cw_block_sum(sx, ex, rs, re, tid) / n, ym = cw_block_sum(sy, ey, rs, re, tid) / n;
+    const double xm = cs_block_sum<CW_NT>(sx, ex, rs, re, tid) / n, ym = cs_block_sum<CW_NT>(sy, ey, rs, re, tid) / n;
     double sxx = 0.0, exx = 0.0, syy = 0.0, eyy = 0.0, sxy = 0.0, exy = 0.0, sd2 = 0.0, ed2 = 0.0;
     for (int k = tid; k < P; k += CW_NT) {
         const int i = qi[k], j = qj[k];
         if (i < 0 || i >= T1 || j < 0 || j >= T2) continue;
         const double x = level ? a0[i] + a1[i] : a0[i], y = level ? b0[j] + b1[j] : b0[j];
         const double dx = x - xm, dy = y - ym, dd = x - y;
-        cw_fma(sxx, exx, dx, dx);
-        cw_fma(syy, eyy, dy, dy);
-        cw_fma(sxy, exy, dx, dy);
-        cw_fma(sd2, ed2, dd, dd);
+        cs_fma(sxx, exx, dx, dx);
+        cs_fma(syy, eyy, dy, dy);
+        cs_fma(sxy, exy, dx, dy);
+        cs_fma(sd2, ed2, dd, dd);
     }
-    const double r0 = cw_block_sum(sxx, exx, rs, re, tid), r1 = cw_block_sum(syy, eyy, rs, re, tid);
-    const double r2 = cw_block_sum(sxy, exy, rs, re, tid), r3 = cw_block_sum(sd2, ed2, rs, re, tid);
+    const double r0 = cs_block_sum<CW_NT>(sxx, exx, rs, re, tid), r1 = cs_block_sum<CW_NT>(syy, eyy, rs, re, tid);
+    const double r2 = cs_block_sum<CW_NT>(sxy, exy, rs, re, tid), r3 = cs_block_sum<CW_NT>(sd2, ed2, rs, re, tid);
     if (tid == 0) {
         o[0] = r0;
         o[1] = r1;

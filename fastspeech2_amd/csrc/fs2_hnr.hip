@@ -3,11 +3,9 @@
 // batches of rows of at most 2048 frames.  The specification is the docstring of fastspeech2_amd/hnr.py; tests/hnr_ref.py restates
 // it in numpy (explicit loops, np.correlate for the lag sums).
 //
-// Every sum here carries its rounding errors in a second word (the two-sum of Knuth for the additions, an fma for the error of
-// each product), per lane in ascending order and then by a fixed tree or in a fixed ascending order: the result is the sum of the
-// exactly evaluated terms rounded once, except in cases too rare to meet.  No atomics; nothing at a frame >= frames[b] is read or
-// written and no sample >= lens[b] is read; the same input gives the same bytes, and a row's bytes do not depend on the rows beside
-// it (a workgroup sees one frame, one row or one pair only).
+// Every sum here is a compensated sum of fs2_comp.h, per lane in ascending order and then by its fixed tree or in a fixed ascending
+// order.  No atomics; nothing at a frame >= frames[b] is read or written and no sample >= lens[b] is read; the same input gives the
+// same bytes, and a row's bytes do not depend on the rows beside it (a workgroup sees one frame, one row or one pair only).
 //
 //   fs2_hnr_frames   one workgroup per frame, the frame in LDS (N = 2 h + 1 doubles, dynamic: up to 64 KiB of the CU's 160).  The
 //                    mean, then a[k] = (x[k] - mean) w[k] in place and r0 = sum a^2.  A lane owns one lag tau and a wave one quarter
@@ -17,7 +15,7 @@
 //   fs2_hnr_side     one workgroup per row: the number, the mean and, in a second pass, the central M2 of hnr over the valid frames.
 //   fs2_hnr_on_path  one workgroup per pair: over the path cells whose two frames are both valid the count and the two means in
 //                    a first pass, Sxx, Syy, Sxy about them and Sd2 in a second.
-#include "fs2_common.h"
+#include "fs2_comp.h"
 
 #define HN_MAX_FRAMES 2048          // = fs2_dtw_max_frames()
 #define HN_MAX_WINDOW 8191
@@ -31,40 +29,6 @@
 #define HN_SILENT 1e-20
 
 #pragma clang fp contract(off)
-
-// (s, e) += p, the rounding error of the addition into e
-static __device__ __forceinline__ void hn_add(double& s, double& e, double p) {
-    const double t = s + p, bb = t - s;
-    e += (s - (t - bb)) + (p - bb);
-    s = t;
-}
-
-// (s, e) += a b, the product taken exactly
-static __device__ __forceinline__ void hn_fma(double& s, double& e, double a, double b) {
-    const double p = a * b;
-    e += __builtin_fma(a, b, -p);
-    hn_add(s, e, p);
-}
-
-// The sum of the lanes' (s, e) by a fixed tree, the same on every run.  Every lane gets it; rs / re may be reused after the call.
-static __device__ __forceinline__ double hn_block_sum(double s, double e, double* rs, double* re, int tid) {
-    rs[tid] = s;
-    re[tid] = e;
-    __syncthreads();
-    for (int o = HN_NT / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            double a = rs[tid], b = re[tid];
-            hn_add(a, b, rs[tid + o]);
-            b += re[tid + o];
-            rs[tid] = a;
-            re[tid] = b;
-        }
-        __syncthreads();
-    }
-    const double r = rs[0] + re[0];
-    __syncthreads();
-    return r;
-}
 
 static __host__ __device__ __forceinline__ size_t hn_lds_doubles(int N, int lmax) { return (size_t)N + (size_t)(lmax + 1) + 4 * HN_NT; }
 
@@ -93,16 +57,16 @@ __global__ void __launch_bounds__(HN_NT) hnr_frames_kernel(const float* __restri
         const long i = first + k;
         const double v = (i >= 0 && i < n) ? (double)yr[i] : 0.0;
         a[k] = v;
-        hn_add(s, e, v);
+        cs_add(s, e, v);
     }
-    const double mu = hn_block_sum(s, e, rs, re, tid) / (double)N;
+    const double mu = cs_block_sum<HN_NT>(s, e, rs, re, tid) / (double)N;
     s = 0.0, e = 0.0;
     for (int k = tid; k < N; k += HN_NT) {                                  // a lane rewrites the entries it wrote
         const double v = (a[k] - mu) * w[k];
         a[k] = v;
-        hn_fma(s, e, v, v);
+        cs_fma(s, e, v, v);
     }
-    const double r0 = hn_block_sum(s, e, rs, re, tid);                      // its barriers publish a[]
+    const double r0 = cs_block_sum<HN_NT>(s, e, rs, re, tid);               // its barriers publish a[]
     double* o = out + (size_t)b * ldo_b + (size_t)t * ldo_t;
     const double f = f0[(size_t)b * ldf + t];
     bool valid = f > 0.0 && r0 > HN_SILENT * (double)N;
@@ -131,14 +95,14 @@ __global__ void __launch_bounds__(HN_NT) hnr_frames_kernel(const float* __restri
         const int k1 = min((wv + 1) * Q, N - (base + c0));                  // the longest lag sum of this chunk: the same for the wave
         s = 0.0, e = 0.0;
         for (int k = wv * Q; k < k1; ++k)
-            if (k < count) hn_fma(s, e, a[k], a[k + tau]);
+            if (k < count) cs_fma(s, e, a[k], a[k + tau]);
         ps[tid] = s;
         pe[tid] = e;
         __syncthreads();
         if (wv == 0 && li < nl) {
             double S = ps[lane], E = pe[lane];
             for (int q = 1; q < HN_WAVES; ++q) {
-                hn_add(S, E, ps[q * HN_WAVE + lane]);
+                cs_add(S, E, ps[q * HN_WAVE + lane]);
                 E += pe[q * HN_WAVE + lane];
             }
             rp[li] = (S + E) / (r0 * rw[tau]);
@@ -171,25 +135,25 @@ __global__ void __launch_bounds__(HN_NT) hnr_side_kernel(const double* __restric
     double s = 0.0, e = 0.0, count = 0.0;
     for (int t = tid; t < T; t += HN_NT) {
         if (q[(size_t)t * ldf_t + 2] != 0.0) {
-            hn_add(s, e, q[(size_t)t * ldf_t + 1]);
+            cs_add(s, e, q[(size_t)t * ldf_t + 1]);
             count += 1.0;
         }
     }
-    const double nv = hn_block_sum(count, 0.0, rs, re, tid);                // small integers: exact
+    const double nv = cs_block_sum<HN_NT>(count, 0.0, rs, re, tid);         // small integers: exact
     double* o = stats + (size_t)b * lds;
     if (!(nv > 0.0)) {                                                      // the same for every lane
         if (tid < 3) o[tid] = 0.0;
         return;
     }
-    const double m = hn_block_sum(s, e, rs, re, tid) / nv;
+    const double m = cs_block_sum<HN_NT>(s, e, rs, re, tid) / nv;
     s = 0.0, e = 0.0;
     for (int t = tid; t < T; t += HN_NT) {
         if (q[(size_t)t * ldf_t + 2] != 0.0) {
             const double d = q[(size_t)t * ldf_t + 1] - m;
-            hn_fma(s, e, d, d);
+            cs_fma(s, e, d, d);
         }
     }
-    const double m2 = hn_block_sum(s, e, rs, re, tid);
+    const double m2 = cs_block_sum<HN_NT>(s, e, rs, re, tid);
     if (tid == 0) {
         o[0] = nv;
         o[1] = m;
@@ -218,17 +182,17 @@ __global__ void __launch_bounds__(HN_NT) hnr_on_path_kernel(const int32_t* __res
         const double* u = a + (size_t)i * lda_t;
         const double* v = bq + (size_t)j * ldb_t;
         if (u[2] == 0.0 || v[2] == 0.0) continue;
-        hn_add(sx, ex, u[1]);
-        hn_add(sy, ey, v[1]);
+        cs_add(sx, ex, u[1]);
+        cs_add(sy, ey, v[1]);
         count += 1.0;
     }
-    const double n = hn_block_sum(count, 0.0, rs, re, tid);
+    const double n = cs_block_sum<HN_NT>(count, 0.0, rs, re, tid);
     double* o = sums + (size_t)p * ldo;
     if (!(n > 0.0)) {                                                       // the same for every lane
         if (tid < 7) o[tid] = 0.0;
         return;
     }
-    const double xm = hn_block_sum(sx, ex, rs, re, tid) / n, ym = hn_block_sum(sy, ey, rs, re, tid) / n;
+    const double xm = cs_block_sum<HN_NT>(sx, ex, rs, re, tid) / n, ym = cs_block_sum<HN_NT>(sy, ey, rs, re, tid) / n;
     double sxx = 0.0, exx = 0.0, syy = 0.0, eyy = 0.0, sxy = 0.0, exy = 0.0, sd2 = 0.0, ed2 = 0.0;
     for (int k = tid; k < P; k += HN_NT) {
         const int i = qi[k], j = qj[k];
@@ -238,13 +202,13 @@ __global__ void __launch_bounds__(HN_NT) hnr_on_path_kernel(const int32_t* __res
         if (u[2] == 0.0 || v[2] == 0.0) continue;
         const double x = u[1], yv = v[1];
         const double dx = x - xm, dy = yv - ym, dd = x - yv;
-        hn_fma(sxx, exx, dx, dx);
-        hn_fma(syy, eyy, dy, dy);
-        hn_fma(sxy, exy, dx, dy);
-        hn_fma(sd2, ed2, dd, dd);
+        cs_fma(sxx, exx, dx, dx);
+        cs_fma(syy, eyy, dy, dy);
+        cs_fma(sxy, exy, dx, dy);
+        cs_fma(sd2, ed2, dd, dd);
     }
-    const double r0 = hn_block_sum(sxx, exx, rs, re, tid), r1 = hn_block_sum(syy, eyy, rs, re, tid);
-    const double r2 = hn_block_sum(sxy, exy, rs, re, tid), r3 = hn_block_sum(sd2, ed2, rs, re, tid);
+    const double r0 = cs_block_sum<HN_NT>(sxx, exx, rs, re, tid), r1 = cs_block_sum<HN_NT>(syy, eyy, rs, re, tid);
+    const double r2 = cs_block_sum<HN_NT>(sxy, exy, rs, re, tid), r3 = cs_block_sum<HN_NT>(sd2, ed2, rs, re, tid);
     if (tid == 0) {
         o[0] = n;
         o[1] = xm;

@@ -3,9 +3,9 @@
 // averaged over bands of bins.  fp64, ragged batches c [B][Tmax][K] with strides in elements and unit stride in k.  The
 // specification is the docstring of fastspeech2_amd/modspec.py; tests/modspec_ref.py restates it in numpy with an FFT.
 //
-// Every sum here runs over its terms in ascending order in one thread and carries its rounding errors in a second word (the
-// two-sum of Knuth for the additions, an fma for the error of each product): the result is the sum of the exactly evaluated terms
-// rounded once, except in cases too rare to meet.  No atomics, no cross-lane reduction: the same input gives the same bytes.
+// Every sum here is a compensated sum of fs2_comp.h over its terms in ascending order in one thread.  No atomics, no cross-lane
+// reduction: the same input gives the same bytes.  The transform's sizes are those of fs2_modspec.h, which the postfilter
+// (fs2_msfilter.hip) shares.
 //
 //   fs2_traj_moments  one thread per (b, k), lanes along k so that a wave reads contiguous coefficients of one frame.  Two passes
 //                     over t < lens[b]: the sum, then the squared differences from mean = sum / T.
@@ -18,14 +18,9 @@
 //                     SIMD this leaves can cover, where a gather through the 32 KiB vector L1 of a 64 KiB table could not.  A lane's
 //                     reads are t entries apart, so an even t costs bank conflicts (a factor of about 3 averaged over t), hidden
 //                     under the arithmetic.  Chosen from the code; neither placement has been timed.
-#include "fs2_common.h"
+#include "fs2_modspec.h"
 
-#define MS_NFFT 4096
-#define MS_HALF (MS_NFFT / 2)
-#define MS_MAX_FRAMES 2048          // = fs2_dtw_max_frames(): N is twice the frame bound
-#define MS_MAX_K 128
 #define MS_MAX_BANDS 16
-#define MS_NT 256
 #define MS_LDS ((2 * MS_NFFT + MS_MAX_FRAMES + MS_HALF + 8) * (int)sizeof(double))
 
 struct MsBands {
@@ -35,20 +30,6 @@ struct MsBands {
 
 #pragma clang fp contract(off)
 
-// (s, e) += p, the rounding error of the addition into e
-static __device__ __forceinline__ void ms_add(double& s, double& e, double p) {
-    const double t = s + p, bb = t - s;
-    e += (s - (t - bb)) + (p - bb);
-    s = t;
-}
-
-// (s, e) += a b, the product taken exactly
-static __device__ __forceinline__ void ms_fma(double& s, double& e, double a, double b) {
-    const double p = a * b;
-    e += __builtin_fma(a, b, -p);
-    ms_add(s, e, p);
-}
-
 __global__ void __launch_bounds__(MS_MAX_K) traj_moments_kernel(const double* __restrict__ c, long ldc_b, long ldc_t,
                                                                 const int32_t* __restrict__ lens, double* __restrict__ mom, long ldm_b,
                                                                 long ldm_k, int Tmax, int K) {
@@ -57,12 +38,12 @@ __global__ void __launch_bounds__(MS_MAX_K) traj_moments_kernel(const double* __
     if (k >= K || T < 1) return;
     const double* x = c + (size_t)b * ldc_b + k;
     double s = 0.0, e = 0.0;
-    for (int t = 0; t < T; ++t) ms_add(s, e, x[(size_t)t * ldc_t]);
+    for (int t = 0; t < T; ++t) cs_add(s, e, x[(size_t)t * ldc_t]);
     const double mean = (s + e) / (double)T;
     double m2 = 0.0, e2 = 0.0;
     for (int t = 0; t < T; ++t) {
         const double d = x[(size_t)t * ldc_t] - mean;
-        ms_fma(m2, e2, d, d);
+        cs_fma(m2, e2, d, d);
     }
     double* q = mom + (size_t)b * ldm_b + (size_t)k * ldm_k;
     q[0] = mean;
@@ -93,15 +74,15 @@ __global__ void __launch_bounds__(MS_NT) modspec_kernel(const double* __restrict
         for (int t = 0; t < T; ++t) {
             const double2 w = tw[idx];
             const double v = x[t];
-            ms_fma(re, ree, v, w.x);
-            ms_fma(im, ime, v, w.y);                                        // the sign of the imaginary part does not reach the power
+            cs_fma(re, ree, v, w.x);
+            cs_fma(im, ime, v, w.y);                                        // the sign of the imaginary part does not reach the power
             idx = (idx + f) & (MS_NFFT - 1);
         }
         re += ree;
         im += ime;
         double p = 0.0, pe = 0.0;
-        ms_fma(p, pe, re, re);
-        ms_fma(p, pe, im, im);
+        cs_fma(p, pe, re, re);
+        cs_fma(p, pe, im, im);
         const double v = log((p + pe) / (double)T + floor_);
         ms[f] = v;
         if (lm) lm[f] = v;
@@ -110,7 +91,7 @@ __global__ void __launch_bounds__(MS_NT) modspec_kernel(const double* __restrict
     if (tid < bands.n) {
         const int lo = bands.lo[tid], hi = bands.hi[tid];
         double s = 0.0, e = 0.0;
-        for (int f = lo; f < hi; ++f) ms_add(s, e, ms[f]);
+        for (int f = lo; f < hi; ++f) cs_add(s, e, ms[f]);
         out[(size_t)b * ldo_b + (size_t)k * ldo_k + tid] = (s + e) / (double)(hi - lo) * (10.0 / 2.302585092994045684);
     }
 }
